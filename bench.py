@@ -50,6 +50,8 @@ if ROOT not in sys.path:
 METRIC = ('frames/s (25 ms/10 ms, 16 kHz) for fbank-40 + MFCC-13 at 1/2/4/8 GPUs')
 BYTES_PER_FRAME = {'fbank40': 480, 'mfcc13': 372, 'mfcc13_delta': 476, 'spectrogram': 1348}
 HBM_PEAK_GBS = 8000.0
+DUMP_MAX_UTTS = 512
+DUMP_MAX_BYTES = 64 * 10**6
 
 
 def parse_args():
@@ -84,7 +86,14 @@ def parse_args():
                          'per GPU; the 10 000 waves of the batch are reused round robin, 1 000 speakers)')
     ap.add_argument('--no-extra', action='store_true',
                     help='skip the MFCC / spectrogram side measurements')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed step computed to DIR/fbank40.npy and DIR/mfcc13.npy (float32 '
+                         '[utterances, frames, bins]; rank 0): a fixed seeded sample of at most %d of its utterances, '
+                         'at most 64 MB in all' % DUMP_MAX_UTTS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def effective_cores():
@@ -528,6 +537,23 @@ def main():
     stream = C.c_void_p()
     _backend.check(L.snf_stream_create(C.byref(stream)))
 
+    # --dump-outputs: the features of a seeded sample of utterances, copied out right behind each timed region
+    # (the side measurements below write the same buffers again)
+    dump, dump_ids = {}, None
+    if args.dump_outputs and rank == 0:
+        k = min(n_utts, DUMP_MAX_UTTS, DUMP_MAX_BYTES // (max(1, frames_per_utt) * (40 + 13) * 4))
+        if k < 1:
+            raise SystemExit('--dump-outputs: the features of one utterance exceed %d bytes' % DUMP_MAX_BYTES)
+        dump_ids = np.sort(np.random.default_rng(0).choice(n_utts, k, replace=False))
+
+    def keep(name, buf, cols):
+        """rows `dump_ids` of `buf`, the [n_utts, frames_per_utt, cols] float32 output of a pass"""
+        host = np.empty((len(dump_ids), frames_per_utt, cols), dtype=np.float32)
+        for j, i in enumerate(dump_ids):
+            _backend.check(L.snf_memcpy_d2h(host[j].ctypes.data_as(C.c_void_p),
+                                            C.c_void_p(buf.ptr + int(i) * host[j].nbytes), host[j].nbytes))
+        dump[name] = host
+
     def timed_region(p, d_dst):
         """K steps of `inner` passes of plan `p` between two barriers + synchronisations -> (seconds of the
         slowest rank, kernel ms of every pass)"""
@@ -559,6 +585,8 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed, kernel_ms = timed_region(plan, d_out)
+    if dump_ids is not None:
+        keep('fbank40', d_out, 40)
 
     ms_per_step = elapsed / args.steps * 1e3
     # frames of the whole job per pass: N x 10 000 utterances (weak) or the one corpus (strong)
@@ -577,6 +605,8 @@ def main():
     for _ in range(args.warmup * inner):
         mfcc_plan.run_device(d_wave.ptr, soff, foff, d_mfcc.ptr, stream=stream.value)
     mfcc_elapsed, mfcc_kernel_ms = timed_region(mfcc_plan, d_mfcc)
+    if dump_ids is not None:
+        keep('mfcc13', d_mfcc, 13)
     value_mfcc13 = job_frames * inner * args.steps / mfcc_elapsed
     mfcc_kms = float(np.mean(mfcc_kernel_ms))
     achieved = total_frames * BYTES_PER_FRAME['fbank40'] / (kms * 1e-3) / 1e9
@@ -1030,6 +1060,11 @@ def main():
             job_frames, kms, args.comm_timeout, download)
         if stub:
             gathered['transport'] = 'stub'
+
+    if dump:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, features in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + '.npy'), features)
 
     if rank == 0:
         line = {

@@ -55,6 +55,33 @@ def test_two_ranks_on_one_gpu(gpu, scaling):
 
 
 @pytest.mark.timeout(600)
+def test_dump_outputs_hold_the_features_of_the_timed_step(gpu, tmp_path):
+    """`--dump-outputs DIR`: with fewer utterances than the sample size every utterance is dumped, in order; what
+    the two timed regions computed matches the CPU oracle"""
+    import numpy as np
+    from conftest import assert_close
+    from oracle import oracle as orc
+    from shennong_amd import synth
+    from shennong_amd.processor import FilterbankProcessor, MfccProcessor
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+           '--inner', '2', '--settle', '2', '--utts', '40', '--no-extra', '--cpu-sample', '0',
+           '--dump-outputs', str(tmp_path)]
+    done = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert done.returncode == 0, done.stderr[-2000:]
+    line = json.loads([x for x in done.stdout.splitlines() if x.startswith('{')][-1])
+    assert line['steps'] == 3 and line['ms_per_step'] > 0
+    assert sorted(os.listdir(tmp_path)) == ['fbank40.npy', 'mfcc13.npy']
+    fbank, mfcc = np.load(tmp_path / 'fbank40.npy'), np.load(tmp_path / 'mfcc13.npy')
+    assert fbank.shape == (40, 298, 40) and mfcc.shape == (40, 298, 13)
+    waves = synth.utterances(0, 40, 48000)
+    for i in (0, 17, 39):
+        assert_close(fbank[i], orc.compute(FilterbankProcessor(num_bins=40, dither=0)._build_options(), waves[i]),
+                     what='dumped fbank %d' % i)
+        assert_close(mfcc[i], orc.compute(MfccProcessor(dither=0)._build_options(), waves[i]),
+                     what='dumped mfcc %d' % i)
+
+
+@pytest.mark.timeout(600)
 def test_stalled_transport_costs_the_gather_not_the_line(gpu):
     line = _launch(['--comm-timeout', '4'], {'SNF_STUB_HANG_AFTER': '1'})
     assert line['value'] > 0 and line['value_mfcc13'] > 0 and line['roofline']['kernel_ms'] > 0
