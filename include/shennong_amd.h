@@ -334,6 +334,53 @@ int snf_set_noise_call(uint64_t call);
  */
 int snf_count_nonfinite_device(int device_id, const float* d_data, uint64_t n, uint64_t* count);
 
+/* ---- diagonal GMM (reference processor/ubm.py, DiagUbmProcessor) -------------------------------
+ * Model in Kaldi's DiagGmm natural form, float32 device buffers: gconsts[num_gauss],
+ * means_invvars[num_gauss x dim], inv_vars[num_gauss x dim] (row-major); frames d_x[n_frames x dim].
+ * L[f, c] = gconsts[c] + x_f . means_invvars[c] - 0.5 x_f^2 . inv_vars[c] ([KALDI-UPSTREAM] diag-gmm.cc
+ * DiagGmm::LogLikelihoods), computed by one device path for every entry point below (kernels_gmm.hip), so
+ * the same (frame, Gaussian) gives the same bits in all of them.  `stream` NULL: the calling thread's own
+ * stream.  Every call waits for its stream before returning; scratch is the calling thread's (no
+ * allocation once grown).  Invalid arguments return SNF_E_INVALID before any device work.
+ */
+/* L for every frame and Gaussian: d_loglikes[n_frames x num_gauss] (DiagGmm::LogLikelihoods). */
+int snf_gmm_loglikes(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                     const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss, float* d_loglikes,
+                     void* stream);
+/* E-step statistics (reference ubm.py:342-343, :625-626 accumulate_from_diag_multi_threaded ->
+ * [KALDI-UPSTREAM] mle-diag-gmm.cc AccumDiagGmm::AccumulateFromDiag): posteriors P = softmax_c(L) * w_f
+ * (d_frame_weights[n_frames], NULL = all ones); d_stats[num_gauss x (2 dim + 1)] float64 device rows
+ * [sum_f P | sum_f P x | sum_f P x^2] (occupancy, mean and variance accumulators), *d_tot_like =
+ * sum_f w_f lse_f (float64, device); d_lse[n_frames] (may be NULL) receives the per-frame log-sum-exp.
+ * Deterministic: no atomics, fixed reduction order. */
+int snf_gmm_accumulate(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_frame_weights,
+                       const float* d_gconsts, const float* d_means_invvars, const float* d_inv_vars,
+                       int32_t num_gauss, double* d_stats, double* d_tot_like, float* d_lse, void* stream);
+/* Top num_gselect Gaussians per frame, best first (reference ubm.py:481-482 gaussian_selection_matrix ->
+ * [KALDI-UPSTREAM] diag-gmm.cc DiagGmm::GaussianSelection): d_gselect[n_frames x num_gselect] int32 and
+ * d_loglike[n_frames] (may be NULL) = log-sum-exp of the selected L.  Order: descending L, equal L to the
+ * higher Gaussian index first (Kaldi's std::sort of (loglike, index) pairs with std::greater). */
+int snf_gmm_gselect(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                    const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss, int32_t num_gselect,
+                    int32_t* d_gselect, float* d_loglike, void* stream);
+/* The same among num_preselect preselected Gaussians per frame, d_preselect[n_frames x num_preselect]
+ * (reference ubm.py:467-478 gaussian_selection_preselect -> [KALDI-UPSTREAM] DiagGmm::
+ * GaussianSelectionPreselect); ties compare the Gaussians' own indices.  num_gselect <= num_preselect;
+ * an index outside [0, num_gauss) fails with SNF_E_INVALID. */
+int snf_gmm_gselect_preselect(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                              const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss,
+                              const int32_t* d_preselect, int32_t num_preselect, int32_t num_gselect,
+                              int32_t* d_gselect, float* d_loglike, void* stream);
+/* Posteriors of a selection (reference ubm.py:549-572 gaussian_selection_to_post, log_likelihoods_preselect +
+ * apply_softmax_): d_post[n_frames x num_gselect] aligned with d_gselect, d_loglike[n_frames] the
+ * log-sum-exp of the selected L.  min_post >= 0: the reference's sequential pruning loop (each entry in
+ * turn: zeroed when below min_post, then the whole row renormalised; a row summing to 0 gets 1 at its
+ * first maximum); min_post < 0: no pruning. */
+int snf_gmm_selection_posteriors(int device_id, const float* d_x, int64_t n_frames, int32_t dim,
+                                 const float* d_gconsts, const float* d_means_invvars, const float* d_inv_vars,
+                                 int32_t num_gauss, const int32_t* d_gselect, int32_t num_gselect, float min_post,
+                                 float* d_post, float* d_loglike, void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

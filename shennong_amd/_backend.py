@@ -39,7 +39,9 @@ EXPORTS = [
     'snf_comm_destroy', 'snf_comm_gatherv', 'snf_comm_allreduce_f64',
     'snf_plan_last_kernel_ms', 'snf_plan_kernel_name', 'snf_set_oom_hook',
     'snf_event_create', 'snf_event_destroy', 'snf_event_record', 'snf_event_elapsed_ms', 'snf_mem_info',
-    'snf_stream_wait_event', 'snf_stream_query', 'snf_event_synchronize', 'snf_wav_scan', 'snf_wav_read_pcm16']
+    'snf_stream_wait_event', 'snf_stream_query', 'snf_event_synchronize', 'snf_wav_scan', 'snf_wav_read_pcm16',
+    'snf_gmm_loglikes', 'snf_gmm_accumulate', 'snf_gmm_gselect', 'snf_gmm_gselect_preselect',
+    'snf_gmm_selection_posteriors']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -151,6 +153,11 @@ def lib():
         L.snf_mem_info.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.snf_wav_scan.argtypes = [C.c_char_p, pi32, pi32, pi64, pi32, pi32]
         L.snf_wav_read_pcm16.argtypes = [C.POINTER(C.c_char_p), i64, pi64, pi64, pi16, pi64, i32, pi32]
+        L.snf_gmm_loglikes.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, vp]
+        L.snf_gmm_accumulate.argtypes = [i32, vp, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.snf_gmm_gselect.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, i32, vp, vp, vp]
+        L.snf_gmm_gselect_preselect.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]
+        L.snf_gmm_selection_posteriors.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)

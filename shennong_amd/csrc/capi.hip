@@ -7,6 +7,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <algorithm>
 #include <memory>
 
 #include "snf_internal.h"
@@ -1763,6 +1764,165 @@ int snf_count_nonfinite_device(int device_id, const float* d_data, uint64_t n, u
               hipStreamSynchronize(t->stream) != hipSuccess))
     rc = set_error(SNF_E_HIP, "non-finite count kernel failed");
   *count = host;
+  return rc;
+}
+
+// ---- diagonal GMM (kernels_gmm.hip) -------------------------------------------------------------
+namespace {
+int gmm_check_model(int64_t F, int32_t D, int32_t C, const float* d_x, const float* d_gconsts, const float* d_mi,
+                    const float* d_iv) {
+  if (F < 0) return set_error(SNF_E_INVALID, "gmm: number of frames < 0");
+  if (D < 1) return set_error(SNF_E_INVALID, "gmm: feature dimension must be at least 1");
+  if (C < 1) return set_error(SNF_E_INVALID, "gmm: number of Gaussians must be at least 1");
+  if (!d_gconsts || !d_mi || !d_iv) return set_error(SNF_E_INVALID, "gmm: null model buffer");
+  if (F > 0 && !d_x) return set_error(SNF_E_INVALID, "gmm: null frames buffer");
+  if (F > (int64_t(1) << 40) / D) return set_error(SNF_E_INVALID, "gmm: frame block too large");
+  return SNF_OK;
+}
+
+// The scratch of the calling thread on `device_id` (no allocation once it has grown) and the stream to
+// run on: the caller's, or the thread's own.  Every gmm call waits for that stream before returning, so
+// the scratch is free again for the next call.
+int gmm_begin(int device_id, size_t bytes, void* stream, ThreadScratch** t, hipStream_t* s) {
+  SNF_HIP_CHECK(hipSetDevice(device_id));
+  *t = thread_scratch(device_id);
+  if (!*t) return SNF_E_HIP;
+  int rc = (*t)->buf.ensure(bytes > 0 ? bytes : 16);
+  if (rc) return rc;
+  *s = stream ? static_cast<hipStream_t>(stream) : (*t)->stream;
+  return SNF_OK;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+}  // namespace
+
+int snf_gmm_loglikes(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                     const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss, float* d_loglikes,
+                     void* stream) {
+  int rc = gmm_check_model(n_frames, dim, num_gauss, d_x, d_gconsts, d_means_invvars, d_inv_vars);
+  if (rc) return rc;
+  if (n_frames > 0 && !d_loglikes) return set_error(SNF_E_INVALID, "gmm: null output buffer");
+  if (n_frames == 0) return SNF_OK;
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, 16, stream, &t, &s);
+  if (rc) return rc;
+  rc = launch_gmm_loglikes(d_x, n_frames, dim, d_gconsts, d_means_invvars, d_inv_vars, num_gauss, d_loglikes, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "gmm loglikes kernel failed");
+  return rc;
+}
+
+int snf_gmm_accumulate(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_frame_weights,
+                       const float* d_gconsts, const float* d_means_invvars, const float* d_inv_vars,
+                       int32_t num_gauss, double* d_stats, double* d_tot_like, float* d_lse, void* stream) {
+  int rc = gmm_check_model(n_frames, dim, num_gauss, d_x, d_gconsts, d_means_invvars, d_inv_vars);
+  if (rc) return rc;
+  if (!d_stats || !d_tot_like) return set_error(SNF_E_INVALID, "gmm: null statistics buffer");
+  const int64_t J = 2 * int64_t(dim) + 1, n = num_gauss * J;
+  if (n_frames == 0) {
+    SNF_HIP_CHECK(hipSetDevice(device_id));
+    SNF_HIP_CHECK(hipMemset(d_stats, 0, sizeof(double) * n));
+    SNF_HIP_CHECK(hipMemset(d_tot_like, 0, sizeof(double)));
+    return SNF_OK;
+  }
+  const int64_t tiles = gmm_tiles(n_frames), chunks = gmm_stats_chunks(n_frames, num_gauss, dim);
+  const size_t b_part = align256(sizeof(double) * chunks * n), b_tl = align256(sizeof(double) * tiles);
+  const size_t b_lse = d_lse ? 0 : align256(sizeof(float) * n_frames);
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, b_part + b_tl + b_lse, stream, &t, &s);
+  if (rc) return rc;
+  char* base = t->buf.as<char>();
+  float* lse = d_lse ? d_lse : reinterpret_cast<float*>(base + b_part + b_tl);
+  rc = launch_gmm_accumulate(d_x, n_frames, dim, d_frame_weights, d_gconsts, d_means_invvars, d_inv_vars, num_gauss,
+                             lse, reinterpret_cast<double*>(base + b_part), reinterpret_cast<double*>(base), d_stats,
+                             d_tot_like, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "gmm accumulate kernels failed");
+  return rc;
+}
+
+int snf_gmm_gselect(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                    const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss, int32_t num_gselect,
+                    int32_t* d_gselect, float* d_loglike, void* stream) {
+  int rc = gmm_check_model(n_frames, dim, num_gauss, d_x, d_gconsts, d_means_invvars, d_inv_vars);
+  if (rc) return rc;
+  if (num_gselect < 1 || num_gselect > num_gauss)
+    return set_error(SNF_E_INVALID, "gmm: num_gselect must be in [1, num_gauss]");
+  if (n_frames > 0 && !d_gselect) return set_error(SNF_E_INVALID, "gmm: null output buffer");
+  if (n_frames == 0) return SNF_OK;
+  // L staged through HBM ~128 MB at a time (multiples of the 64-frame tile)
+  int64_t rows = std::max<int64_t>(64, ((int64_t(32) << 20) / num_gauss) & ~int64_t(63));
+  rows = std::min(rows, (n_frames + 63) & ~int64_t(63));
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, sizeof(float) * rows * num_gauss, stream, &t, &s);
+  if (rc) return rc;
+  float* L = t->buf.as<float>();
+  for (int64_t a = 0; a < n_frames && !rc; a += rows) {
+    const int64_t r = std::min(rows, n_frames - a);
+    rc = launch_gmm_loglikes(d_x + a * dim, r, dim, d_gconsts, d_means_invvars, d_inv_vars, num_gauss, L, s);
+    if (!rc)
+      rc = launch_gmm_topn(L, nullptr, r, num_gauss, num_gselect, d_gselect + a * num_gselect,
+                           d_loglike ? d_loglike + a : nullptr, s);
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "gmm gselect kernels failed");
+  return rc;
+}
+
+int snf_gmm_gselect_preselect(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                              const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss,
+                              const int32_t* d_preselect, int32_t num_preselect, int32_t num_gselect,
+                              int32_t* d_gselect, float* d_loglike, void* stream) {
+  int rc = gmm_check_model(n_frames, dim, num_gauss, d_x, d_gconsts, d_means_invvars, d_inv_vars);
+  if (rc) return rc;
+  if (num_preselect < 1) return set_error(SNF_E_INVALID, "gmm: num_preselect must be at least 1");
+  if (num_gselect < 1 || num_gselect > num_preselect)
+    return set_error(SNF_E_INVALID, "gmm: num_gselect must be in [1, num_preselect]");
+  if (n_frames > 0 && (!d_preselect || !d_gselect)) return set_error(SNF_E_INVALID, "gmm: null selection buffer");
+  if (n_frames == 0) return SNF_OK;
+  const size_t b_l = align256(sizeof(float) * n_frames * num_preselect);
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, b_l + sizeof(int), stream, &t, &s);
+  if (rc) return rc;
+  float* L = t->buf.as<float>();
+  int* d_bad = reinterpret_cast<int*>(t->buf.as<char>() + b_l);
+  int bad = 0;
+  SNF_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+  rc = launch_gmm_sel_loglikes(d_x, n_frames, dim, d_gconsts, d_means_invvars, d_inv_vars, num_gauss, d_preselect,
+                               num_preselect, L, d_bad, s);
+  if (!rc) rc = launch_gmm_topn(L, d_preselect, n_frames, num_preselect, num_gselect, d_gselect, d_loglike, s);
+  if (!rc && hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess)
+    rc = set_error(SNF_E_HIP, "gmm preselect: copy failed");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "gmm preselect kernels failed");
+  if (!rc && bad) rc = set_error(SNF_E_INVALID, "gmm: preselected Gaussian index out of range");
+  return rc;
+}
+
+int snf_gmm_selection_posteriors(int device_id, const float* d_x, int64_t n_frames, int32_t dim,
+                                 const float* d_gconsts, const float* d_means_invvars, const float* d_inv_vars,
+                                 int32_t num_gauss, const int32_t* d_gselect, int32_t num_gselect, float min_post,
+                                 float* d_post, float* d_loglike, void* stream) {
+  int rc = gmm_check_model(n_frames, dim, num_gauss, d_x, d_gconsts, d_means_invvars, d_inv_vars);
+  if (rc) return rc;
+  if (num_gselect < 1) return set_error(SNF_E_INVALID, "gmm: num_gselect must be at least 1");
+  if (n_frames > 0 && (!d_gselect || !d_post || !d_loglike))
+    return set_error(SNF_E_INVALID, "gmm: null selection buffer");
+  if (n_frames == 0) return SNF_OK;
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, sizeof(int), stream, &t, &s);
+  if (rc) return rc;
+  int* d_bad = t->buf.as<int>();
+  int bad = 0;
+  SNF_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+  rc = launch_gmm_sel_loglikes(d_x, n_frames, dim, d_gconsts, d_means_invvars, d_inv_vars, num_gauss, d_gselect,
+                               num_gselect, d_post, d_bad, s);
+  if (!rc) rc = launch_gmm_post(d_post, n_frames, num_gselect, min_post, min_post >= 0.0f, d_loglike, s);
+  if (!rc && hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess)
+    rc = set_error(SNF_E_HIP, "gmm posteriors: copy failed");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "gmm posteriors kernels failed");
+  if (!rc && bad) rc = set_error(SNF_E_INVALID, "gmm: selected Gaussian index out of range");
   return rc;
 }
 

@@ -349,6 +349,20 @@ struct PitchPostParams {
 int launch_pitch_post(const PitchPostParams& p, const float* in, const int64_t* frame_offsets,
                       int64_t n_utts, int64_t total_frames, float* out, hipStream_t stream);
 
+// GMM kernels (kernels_gmm.hip): see that file's header for the design
+int64_t gmm_stats_chunks(int64_t F, int C, int D);
+int64_t gmm_tiles(int64_t F);
+int launch_gmm_loglikes(const float* x, int64_t F, int D, const float* gconst, const float* mi, const float* iv, int C,
+                        float* out, hipStream_t stream);
+int launch_gmm_accumulate(const float* x, int64_t F, int D, const float* weights, const float* gconst,
+                          const float* mi, const float* iv, int C, float* lse, double* tl_part, double* part,
+                          double* stats, double* tot_like, hipStream_t stream);
+int launch_gmm_topn(const float* L, const int32_t* map, int64_t rows, int P, int n, int32_t* out_idx, float* out_lse,
+                    hipStream_t stream);
+int launch_gmm_sel_loglikes(const float* x, int64_t F, int D, const float* gconst, const float* mi, const float* iv,
+                            int C, const int32_t* sel, int P, float* out, int* bad, hipStream_t stream);
+int launch_gmm_post(float* post, int64_t F, int n, float min_post, int prune, float* loglike, hipStream_t stream);
+
 }  // namespace snf
 
 #endif  // SNF_INTERNAL_H_

@@ -10,7 +10,9 @@ utterances instead of a per-utterance thread pool:
     -> [pitch -> pitch post-processing] -> CMVN apply -> delta -> pitch concatenation (tolerance 2)
 
 Not provided by this backend (out of scope): VTLN *training* (`with_vtln`, the 'vtln'
-configuration entry; precomputed `warps` are supported), CREPE pitch, bottleneck features.
+configuration entry; precomputed `warps` are supported), CREPE pitch, bottleneck features.  The UBM that
+VTLN training builds on is in scope: :class:`~shennong_amd.processor.ubm.DiagUbmProcessor` (diagonal GMM,
+HIP E-step); ``VtlnProcessor`` (Kaldi LinearVtln + FMLLR statistics) is the next piece of work.
 """
 
 import os

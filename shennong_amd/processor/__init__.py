@@ -14,6 +14,7 @@ _HOME = {
     'SpectrogramProcessor': 'spectrogram',
     'KaldiPitchProcessor': 'pitch_kaldi',
     'KaldiPitchPostProcessor': 'pitch_kaldi',
+    'DiagUbmProcessor': 'ubm',
 }
 __all__ = sorted(_HOME)
 

@@ -278,6 +278,56 @@ def _write_matrix(stream, key, mat, double):
     return offset
 
 
+def write_kaldi_token(stream, token):
+    """Kaldi WriteToken in binary mode: the token and one space"""
+    stream.write(token.encode('ascii') + b' ')
+
+
+def write_kaldi_object(stream, array):
+    """A float32 Kaldi Vector (``FV``) or Matrix (``FM``) in binary mode, the layout `_write_matrix` writes
+    for a table entry without the key and the binary marker"""
+    array = np.ascontiguousarray(array, dtype=np.float32)
+    if array.ndim == 1:
+        stream.write(b'FV \4' + struct.pack('<i', array.shape[0]))
+    else:
+        stream.write(b'FM \4' + struct.pack('<i', array.shape[0]) + b'\4' + struct.pack('<i', array.shape[1]))
+    stream.write(array.tobytes())
+
+
+class KaldiBinaryReader:
+    """Reads back what `write_kaldi_token` / `write_kaldi_object` wrote (float or double objects)"""
+    def __init__(self, blob, pos=0):
+        self.blob, self.pos = blob, pos
+
+    def token(self):
+        end = self.blob.index(b' ', self.pos)
+        tok, self.pos = self.blob[self.pos:end].decode('ascii'), end + 1
+        return tok
+
+    def expect(self, token):
+        got = self.token()
+        if got != token:
+            raise ValueError(f'expected token {token}, got {got}')
+
+    def _int(self):
+        if self.blob[self.pos:self.pos + 1] != b'\4':
+            raise ValueError('bad integer size marker in Kaldi binary object')
+        value = struct.unpack('<i', self.blob[self.pos + 1:self.pos + 5])[0]
+        self.pos += 5
+        return value
+
+    def object(self):
+        kind = self.token()
+        if kind not in ('FV', 'DV', 'FM', 'DM'):
+            raise ValueError(f'not a Kaldi vector or matrix: {kind}')
+        dtype = np.dtype('<f4' if kind[0] == 'F' else '<f8')
+        shape = (self._int(),) if kind[1] == 'V' else (self._int(), self._int())
+        count = int(np.prod(shape))
+        out = np.frombuffer(self.blob, dtype=dtype, count=count, offset=self.pos).reshape(shape)
+        self.pos += count * dtype.itemsize
+        return out.astype(np.float32)
+
+
 def _read_table(ark):
     """key -> float64 matrix of a binary archive of double or float matrices"""
     with open(ark, 'rb') as stream:
