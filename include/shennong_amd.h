@@ -381,6 +381,42 @@ int snf_gmm_selection_posteriors(int device_id, const float* d_x, int64_t n_fram
                                  int32_t num_gauss, const int32_t* d_gselect, int32_t num_gselect, float min_post,
                                  float* d_post, float* d_loglike, void* stream);
 
+/* ---- linear VTLN (reference processor/vtln.py, VtlnProcessor) ----------------------------------
+ * Segments: contiguous runs of frames, h_seg_offsets[n_segments + 1] (HOST int64, non-decreasing, first 0,
+ * last n_frames); a segment may be empty.  dim <= 64.  Model buffers as in the snf_gmm_* block.  Outputs are
+ * float64 sums over fixed-order partials (no atomics): the same inputs give the same bits.  `stream` NULL:
+ * the calling thread's own stream; every call waits for its stream before returning.  Invalid arguments
+ * return SNF_E_INVALID before any device work.
+ */
+/* fMLLR statistics per segment ([KALDI-UPSTREAM] fmllr-diag-gmm.cc FmllrDiagGmmAccs::
+ * AccumulateFromPosteriorsPreselect, reference vtln.py:434-441): d_gselect / d_post [n_frames x num_gselect]
+ * (int32 / float32, pruned posteriors 0), 1 <= num_gselect <= 64.  d_stats[n_segments x U x (dim + 1)]
+ * float64 with U = dim (dim + 1) + dim + 1 and x+ = [x | 1]: rows d (dim + 1) + k hold G[d][k][:] =
+ * sum_f b_f[d] x+_k x+, rows dim (dim + 1) + d hold K[d][:] = sum_f a_f[d] x+, the last row sum_f count_f x+
+ * (its last entry is beta); a_f / b_f / count_f = sum_j p_fj means_invvars / inv_vars / 1 of g_fj. */
+int snf_fmllr_accumulate(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const int32_t* d_gselect,
+                         const float* d_post, int32_t num_gselect, const float* d_means_invvars,
+                         const float* d_inv_vars, int32_t num_gauss, const int64_t* h_seg_offsets,
+                         int64_t n_segments, double* d_stats, void* stream);
+/* d_gram[(2 dim + 1) x (2 dim + 1)] float64 = sum_f w_f z_f z_f^T, z = [x | 1 | y] (the sums of reference
+ * vtln.py:299-343, gmm-train-lvtln-special); d_weights[n_frames] NULL = all ones. */
+int snf_vtln_gram(int device_id, const float* d_x, const float* d_y, const float* d_weights, int64_t n_frames,
+                  int32_t dim, double* d_gram, void* stream);
+/* Class search per segment over the statistics of snf_fmllr_accumulate ([KALDI-UPSTREAM] lvtln.cc
+ * LinearVtln::ComputeTransform): d_A[num_classes x dim x dim] and d_logdets[num_classes] float64;
+ * norm_type 0 none, 1 offset, 2 diag; outputs d_objf[n_segments x num_classes] float64 (every class's
+ * objective), d_class[n_segments] int32 (first maximum), d_impr / d_count[n_segments] float64 and
+ * d_transform[n_segments x dim x (dim + 1)] float32.  beta = 0: default_class, [A_default | 0], 0, 0. */
+int snf_lvtln_select(int device_id, const double* d_stats, int64_t n_segments, int32_t dim, const double* d_A,
+                     const double* d_logdets, int32_t num_classes, int32_t norm_type, double logdet_scale,
+                     int32_t default_class, double* d_objf, int32_t* d_class, double* d_impr, double* d_count,
+                     float* d_transform, void* stream);
+/* d_y[f] = W_s[:, :dim] x_f + W_s[:, dim] for the segment s of frame f, d_transforms[n_segments x dim x
+ * (dim + 1)] float32 (reference vtln.py:659-665). */
+int snf_affine_apply_segments(int device_id, const float* d_x, int64_t n_frames, int32_t dim,
+                              const int64_t* h_seg_offsets, int64_t n_segments, const float* d_transforms,
+                              float* d_y, void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

@@ -41,7 +41,8 @@ EXPORTS = [
     'snf_event_create', 'snf_event_destroy', 'snf_event_record', 'snf_event_elapsed_ms', 'snf_mem_info',
     'snf_stream_wait_event', 'snf_stream_query', 'snf_event_synchronize', 'snf_wav_scan', 'snf_wav_read_pcm16',
     'snf_gmm_loglikes', 'snf_gmm_accumulate', 'snf_gmm_gselect', 'snf_gmm_gselect_preselect',
-    'snf_gmm_selection_posteriors']
+    'snf_gmm_selection_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
+    'snf_affine_apply_segments']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -158,6 +159,11 @@ def lib():
         L.snf_gmm_gselect.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, i32, vp, vp, vp]
         L.snf_gmm_gselect_preselect.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]
         L.snf_gmm_selection_posteriors.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
+        L.snf_fmllr_accumulate.argtypes = [i32, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, vp, vp]
+        L.snf_vtln_gram.argtypes = [i32, vp, vp, vp, i64, i32, vp, vp]
+        L.snf_lvtln_select.argtypes = [i32, vp, i64, i32, vp, vp, i32, i32, C.c_double, i32, vp, vp, vp, vp, vp,
+                                       vp]
+        L.snf_affine_apply_segments.argtypes = [i32, vp, i64, i32, vp, i64, vp, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)

@@ -1926,6 +1926,170 @@ int snf_gmm_selection_posteriors(int device_id, const float* d_x, int64_t n_fram
   return rc;
 }
 
+// ---- linear VTLN (kernels_vtln.hip) -------------------------------------------------------------
+namespace {
+int vtln_check_segments(const int64_t* off, int64_t S, int64_t F) {
+  if (S < 0) return set_error(SNF_E_INVALID, "vtln: number of segments < 0");
+  if (!off) return set_error(SNF_E_INVALID, "vtln: null segment offsets");
+  if (off[0] != 0 || off[S] != F) return set_error(SNF_E_INVALID, "vtln: segment offsets must run from 0 to n_frames");
+  for (int64_t s = 0; s < S; ++s)
+    if (off[s + 1] < off[s]) return set_error(SNF_E_INVALID, "vtln: segment offsets must be non-decreasing");
+  return SNF_OK;
+}
+
+// Items of at most vtln_item_frames() frames per segment: (first, end, slot) with slot = the segment when it
+// has one item, else n_segments + its partial's index; red = (segment, first partial, count) per split segment.
+void vtln_items(const int64_t* off, int64_t S, std::vector<int64_t>* items, std::vector<int64_t>* red,
+                int64_t* n_part) {
+  const int64_t chunk = vtln_item_frames();
+  *n_part = 0;
+  for (int64_t s = 0; s < S; ++s) {
+    const int64_t len = off[s + 1] - off[s];
+    if (len == 0) continue;
+    const int64_t nch = (len + chunk - 1) / chunk;
+    if (nch == 1) {
+      items->insert(items->end(), {off[s], off[s + 1], s});
+      continue;
+    }
+    red->insert(red->end(), {s, *n_part, nch});
+    for (int64_t c = 0; c < nch; ++c) {
+      const int64_t a = off[s] + c * chunk;
+      items->insert(items->end(), {a, std::min(off[s + 1], a + chunk), S + (*n_part)++});
+    }
+  }
+}
+}  // namespace
+
+int snf_fmllr_accumulate(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const int32_t* d_gselect,
+                         const float* d_post, int32_t num_gselect, const float* d_means_invvars,
+                         const float* d_inv_vars, int32_t num_gauss, const int64_t* h_seg_offsets,
+                         int64_t n_segments, double* d_stats, void* stream) {
+  if (n_frames < 0) return set_error(SNF_E_INVALID, "vtln: number of frames < 0");
+  if (dim < 1 || dim > 64) return set_error(SNF_E_INVALID, "vtln: feature dimension must be in [1, 64]");
+  if (num_gauss < 1) return set_error(SNF_E_INVALID, "vtln: number of Gaussians must be at least 1");
+  if (num_gselect < 1 || num_gselect > 64) return set_error(SNF_E_INVALID, "vtln: num_gselect must be in [1, 64]");
+  if (!d_means_invvars || !d_inv_vars) return set_error(SNF_E_INVALID, "vtln: null model buffer");
+  if (n_frames > 0 && (!d_x || !d_gselect || !d_post)) return set_error(SNF_E_INVALID, "vtln: null frames buffer");
+  if (n_frames > (int64_t(1) << 28)) return set_error(SNF_E_INVALID, "vtln: frame block too large");
+  int rc = vtln_check_segments(h_seg_offsets, n_segments, n_frames);
+  if (rc) return rc;
+  if (n_segments > 0 && !d_stats) return set_error(SNF_E_INVALID, "vtln: null statistics buffer");
+  if (n_segments == 0) return SNF_OK;
+  const int64_t V = dim + 1, U = int64_t(dim) * V + dim + 1, uv = U * V;
+  std::vector<int64_t> items, red;
+  int64_t n_part = 0;
+  vtln_items(h_seg_offsets, n_segments, &items, &red, &n_part);
+  const size_t b_rec = align256(sizeof(double) * std::max<int64_t>(1, n_frames) * (3 * dim + 2));
+  const size_t b_part = align256(sizeof(double) * n_part * uv);
+  const size_t b_items = align256(sizeof(int64_t) * (items.size() + 3)), b_red = align256(sizeof(int64_t) * (red.size() + 3));
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, b_rec + b_part + b_items + b_red + sizeof(int), stream, &t, &s);
+  if (rc) return rc;
+  char* base = t->buf.as<char>();
+  double* rec = reinterpret_cast<double*>(base);
+  double* part = reinterpret_cast<double*>(base + b_rec);
+  int64_t* d_items = reinterpret_cast<int64_t*>(base + b_rec + b_part);
+  int64_t* d_red = reinterpret_cast<int64_t*>(base + b_rec + b_part + b_items);
+  int* d_bad = reinterpret_cast<int*>(base + b_rec + b_part + b_items + b_red);
+  int bad = 0;
+  SNF_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), s));
+  SNF_HIP_CHECK(hipMemsetAsync(d_stats, 0, sizeof(double) * n_segments * uv, s));
+  if (!items.empty())
+    SNF_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), sizeof(int64_t) * items.size(), hipMemcpyHostToDevice, s));
+  if (!red.empty())
+    SNF_HIP_CHECK(hipMemcpyAsync(d_red, red.data(), sizeof(int64_t) * red.size(), hipMemcpyHostToDevice, s));
+  rc = launch_fmllr_accumulate(d_x, n_frames, dim, d_gselect, d_post, num_gselect, d_means_invvars, d_inv_vars,
+                               num_gauss, rec, d_bad, d_items, int64_t(items.size() / 3), n_segments, d_stats, part,
+                               d_red, int64_t(red.size() / 3), s);
+  if (!rc && hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess)
+    rc = set_error(SNF_E_HIP, "fmllr accumulate: copy failed");
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "fmllr accumulate kernels failed");
+  if (!rc && bad) rc = set_error(SNF_E_INVALID, "vtln: selected Gaussian index out of range");
+  return rc;
+}
+
+int snf_vtln_gram(int device_id, const float* d_x, const float* d_y, const float* d_weights, int64_t n_frames,
+                  int32_t dim, double* d_gram, void* stream) {
+  if (n_frames < 0) return set_error(SNF_E_INVALID, "vtln: number of frames < 0");
+  if (dim < 1 || dim > 64) return set_error(SNF_E_INVALID, "vtln: feature dimension must be in [1, 64]");
+  if (n_frames > 0 && (!d_x || !d_y)) return set_error(SNF_E_INVALID, "vtln: null frames buffer");
+  if (!d_gram) return set_error(SNF_E_INVALID, "vtln: null output buffer");
+  if (n_frames > (int64_t(1) << 28)) return set_error(SNF_E_INVALID, "vtln: frame block too large");
+  const int64_t V = 2 * int64_t(dim) + 1, uv = V * V;
+  const int64_t off[2] = {0, n_frames};
+  std::vector<int64_t> items, red;
+  int64_t n_part = 0;
+  vtln_items(off, 1, &items, &red, &n_part);
+  const size_t b_rec = align256(sizeof(double) * std::max<int64_t>(1, n_frames) * (2 * dim + 2));
+  const size_t b_part = align256(sizeof(double) * n_part * uv);
+  const size_t b_items = align256(sizeof(int64_t) * (items.size() + 3));
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  int rc = gmm_begin(device_id, b_rec + b_part + b_items + sizeof(int64_t) * (red.size() + 3), stream, &t, &s);
+  if (rc) return rc;
+  char* base = t->buf.as<char>();
+  double* rec = reinterpret_cast<double*>(base);
+  double* part = reinterpret_cast<double*>(base + b_rec);
+  int64_t* d_items = reinterpret_cast<int64_t*>(base + b_rec + b_part);
+  int64_t* d_red = reinterpret_cast<int64_t*>(base + b_rec + b_part + b_items);
+  SNF_HIP_CHECK(hipMemsetAsync(d_gram, 0, sizeof(double) * uv, s));
+  if (!items.empty())
+    SNF_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), sizeof(int64_t) * items.size(), hipMemcpyHostToDevice, s));
+  if (!red.empty())
+    SNF_HIP_CHECK(hipMemcpyAsync(d_red, red.data(), sizeof(int64_t) * red.size(), hipMemcpyHostToDevice, s));
+  rc = launch_vtln_gram(d_x, d_y, d_weights, n_frames, dim, rec, d_items, int64_t(items.size() / 3), d_gram, part,
+                        d_red, int64_t(red.size() / 3), s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "vtln gram kernels failed");
+  return rc;
+}
+
+int snf_lvtln_select(int device_id, const double* d_stats, int64_t n_segments, int32_t dim, const double* d_A,
+                     const double* d_logdets, int32_t num_classes, int32_t norm_type, double logdet_scale,
+                     int32_t default_class, double* d_objf, int32_t* d_class, double* d_impr, double* d_count,
+                     float* d_transform, void* stream) {
+  if (n_segments < 0) return set_error(SNF_E_INVALID, "vtln: number of segments < 0");
+  if (dim < 1 || dim > 64) return set_error(SNF_E_INVALID, "vtln: feature dimension must be in [1, 64]");
+  if (num_classes < 1) return set_error(SNF_E_INVALID, "vtln: number of classes must be at least 1");
+  if (default_class < 0 || default_class >= num_classes)
+    return set_error(SNF_E_INVALID, "vtln: default class must be in [0, num_classes)");
+  if (norm_type < 0 || norm_type > 2) return set_error(SNF_E_INVALID, "vtln: norm_type must be 0, 1 or 2");
+  if (!std::isfinite(logdet_scale)) return set_error(SNF_E_INVALID, "vtln: logdet_scale must be finite");
+  if (!d_A || !d_logdets) return set_error(SNF_E_INVALID, "vtln: null model buffer");
+  if (n_segments > 0 && (!d_stats || !d_objf || !d_class || !d_impr || !d_count || !d_transform))
+    return set_error(SNF_E_INVALID, "vtln: null statistics or output buffer");
+  if (n_segments == 0) return SNF_OK;
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  int rc = gmm_begin(device_id, 16, stream, &t, &s);
+  if (rc) return rc;
+  rc = launch_lvtln_select(d_stats, n_segments, dim, d_A, d_logdets, num_classes, norm_type, logdet_scale,
+                           default_class, d_objf, d_class, d_impr, d_count, d_transform, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "lvtln select kernel failed");
+  return rc;
+}
+
+int snf_affine_apply_segments(int device_id, const float* d_x, int64_t n_frames, int32_t dim,
+                              const int64_t* h_seg_offsets, int64_t n_segments, const float* d_transforms,
+                              float* d_y, void* stream) {
+  if (n_frames < 0) return set_error(SNF_E_INVALID, "vtln: number of frames < 0");
+  if (dim < 1 || dim > 64) return set_error(SNF_E_INVALID, "vtln: feature dimension must be in [1, 64]");
+  if (n_frames > (int64_t(1) << 28)) return set_error(SNF_E_INVALID, "vtln: frame block too large");
+  int rc = vtln_check_segments(h_seg_offsets, n_segments, n_frames);
+  if (rc) return rc;
+  if (n_frames > 0 && (!d_x || !d_y || !d_transforms)) return set_error(SNF_E_INVALID, "vtln: null buffer");
+  if (n_frames == 0) return SNF_OK;
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, sizeof(int64_t) * (n_segments + 1), stream, &t, &s);
+  if (rc) return rc;
+  int64_t* d_off = t->buf.as<int64_t>();
+  SNF_HIP_CHECK(hipMemcpyAsync(d_off, h_seg_offsets, sizeof(int64_t) * (n_segments + 1), hipMemcpyHostToDevice, s));
+  rc = launch_affine_apply_segments(d_x, n_frames, dim, d_off, n_segments, d_transforms, d_y, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "affine apply kernel failed");
+  return rc;
+}
+
 int snf_malloc(void** dptr, uint64_t bytes) {
   SNF_HIP_CHECK(hipMalloc(dptr, bytes));
   return SNF_OK;

@@ -363,6 +363,21 @@ int launch_gmm_sel_loglikes(const float* x, int64_t F, int D, const float* gcons
                             int C, const int32_t* sel, int P, float* out, int* bad, hipStream_t stream);
 int launch_gmm_post(float* post, int64_t F, int n, float min_post, int prune, float* loglike, hipStream_t stream);
 
+// linear-VTLN kernels (kernels_vtln.hip): see that file's header for the design
+int64_t vtln_item_frames();
+int launch_fmllr_accumulate(const float* x, int64_t F, int D, const int32_t* sel, const float* post, int n,
+                            const float* mi, const float* iv, int C, double* rec, int* bad, const int64_t* items,
+                            int64_t n_items, int64_t S, double* out, double* part, const int64_t* red, int64_t n_red,
+                            hipStream_t stream);
+int launch_vtln_gram(const float* x, const float* y, const float* w, int64_t F, int D, double* rec,
+                     const int64_t* items, int64_t n_items, double* out, double* part, const int64_t* red,
+                     int64_t n_red, hipStream_t stream);
+int launch_lvtln_select(const double* stats, int64_t S, int D, const double* A, const double* logdets, int C,
+                        int norm_type, double logdet_scale, int default_class, double* objf, int32_t* cls,
+                        double* impr, double* count, float* transform, hipStream_t stream);
+int launch_affine_apply_segments(const float* x, int64_t F, int D, const int64_t* off, int64_t S, const float* W,
+                                 float* y, hipStream_t stream);
+
 }  // namespace snf
 
 #endif  // SNF_INTERNAL_H_

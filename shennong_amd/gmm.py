@@ -341,6 +341,40 @@ class FrameBlock:
             self.weights = _backend.DeviceBuffer(4 * max(1, self.nframes), self.device)
             self.weights.upload(w)
 
+    @classmethod
+    def from_device(cls, frames, offsets, dim, device=None):
+        """A block over an existing device buffer of float32 [F, D] frames (no copy): e.g. the output of
+        :func:`shennong_amd.lvtln.affine_apply_segments`"""
+        block = cls.__new__(cls)
+        block.dim = int(dim)
+        block.offsets = np.asarray(offsets, dtype=np.int64).copy()
+        block.nframes = int(block.offsets[-1])
+        block.device = frames.device if device is None else int(device)
+        block.frames = frames
+        block.weights = None
+        return block
+
+    def upload_selection(self, selection):
+        """A selection [F, n] int32 in HBM, uploaded once for several :meth:`selection_posteriors_device`"""
+        sel = np.ascontiguousarray(selection, dtype=np.int32)
+        if sel.ndim != 2 or sel.shape[0] != self.nframes:
+            raise ValueError('selection must be [frames, n]')
+        dsel = _backend.DeviceBuffer(max(16, sel.nbytes), self.device)
+        dsel.upload(sel)
+        return dsel
+
+    def selection_posteriors_device(self, dgmm, dsel, num_gselect, min_post=None):
+        """:meth:`selection_posteriors` of a selection already in HBM (`dsel`, [F, num_gselect] int32); the
+        posteriors stay on the device: a DeviceBuffer [F, num_gselect] float32"""
+        self._check(dgmm)
+        F, n = self.nframes, int(num_gselect)
+        post = _backend.DeviceBuffer(4 * max(1, F * n), self.device)
+        like = _backend.DeviceBuffer(4 * max(1, F), self.device)
+        _backend.check(_backend.lib().snf_gmm_selection_posteriors(
+            self.device, C.c_void_p(self.frames.ptr), F, self.dim, *dgmm.args(), C.c_void_p(dsel.ptr), n,
+            -1.0 if min_post is None else float(min_post), C.c_void_p(post.ptr), C.c_void_p(like.ptr), None))
+        return post
+
     def split(self, values):
         """Rows of a per-frame host array, per utterance"""
         return [values[a:b] for a, b in zip(self.offsets[:-1], self.offsets[1:])]

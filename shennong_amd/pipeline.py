@@ -9,10 +9,11 @@ utterances instead of a per-utterance thread pool:
     features (+ VTLN warps) -> [energy -> VAD -> CMVN statistics per speaker / utterance]
     -> [pitch -> pitch post-processing] -> CMVN apply -> delta -> pitch concatenation (tolerance 2)
 
-Not provided by this backend (out of scope): VTLN *training* (`with_vtln`, the 'vtln'
-configuration entry; precomputed `warps` are supported), CREPE pitch, bottleneck features.  The UBM that
-VTLN training builds on is in scope: :class:`~shennong_amd.processor.ubm.DiagUbmProcessor` (diagonal GMM,
-HIP E-step); ``VtlnProcessor`` (Kaldi LinearVtln + FMLLR statistics) is the next piece of work.
+Not provided by this pipeline: VTLN training through the configuration (`with_vtln`, the 'vtln' entry),
+CREPE pitch, bottleneck features.  VTLN training itself is available as
+:class:`~shennong_amd.processor.vtln.VtlnProcessor` (over the
+:class:`~shennong_amd.processor.ubm.DiagUbmProcessor` UBM); give the warps its ``process`` returns to
+:func:`extract_features` (``warps=...``).
 """
 
 import os

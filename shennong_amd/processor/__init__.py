@@ -15,6 +15,7 @@ _HOME = {
     'KaldiPitchProcessor': 'pitch_kaldi',
     'KaldiPitchPostProcessor': 'pitch_kaldi',
     'DiagUbmProcessor': 'ubm',
+    'VtlnProcessor': 'vtln',
 }
 __all__ = sorted(_HOME)
 
