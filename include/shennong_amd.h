@@ -402,6 +402,13 @@ int snf_fmllr_accumulate(int device_id, const float* d_x, int64_t n_frames, int3
  * vtln.py:299-343, gmm-train-lvtln-special); d_weights[n_frames] NULL = all ones. */
 int snf_vtln_gram(int device_id, const float* d_x, const float* d_y, const float* d_weights, int64_t n_frames,
                   int32_t dim, double* d_gram, void* stream);
+/* snf_vtln_gram over rows gathered from blocks: record f takes row d_row[f] of block d_block[f] of both
+ * d_x_blocks and d_y_blocks (DEVICE arrays of DEVICE pointers, each block row-major [rows x dim] float32);
+ * d_weights[n_frames] NULL = all ones.  The caller keeps every (block, row) in range.  The result equals,
+ * bit for bit, snf_vtln_gram on the same rows gathered in the same order. */
+int snf_vtln_gram_rows(int device_id, const float* const* d_x_blocks, const float* const* d_y_blocks,
+                       const int32_t* d_block, const int64_t* d_row, const float* d_weights,
+                       int64_t n_frames, int32_t dim, double* d_gram, void* stream);
 /* Class search per segment over the statistics of snf_fmllr_accumulate ([KALDI-UPSTREAM] lvtln.cc
  * LinearVtln::ComputeTransform): d_A[num_classes x dim x dim] and d_logdets[num_classes] float64;
  * norm_type 0 none, 1 offset, 2 diag; outputs d_objf[n_segments x num_classes] float64 (every class's

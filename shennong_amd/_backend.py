@@ -42,7 +42,7 @@ EXPORTS = [
     'snf_stream_wait_event', 'snf_stream_query', 'snf_event_synchronize', 'snf_wav_scan', 'snf_wav_read_pcm16',
     'snf_gmm_loglikes', 'snf_gmm_accumulate', 'snf_gmm_gselect', 'snf_gmm_gselect_preselect',
     'snf_gmm_selection_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
-    'snf_affine_apply_segments']
+    'snf_affine_apply_segments', 'snf_vtln_gram_rows']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -161,6 +161,7 @@ def lib():
         L.snf_gmm_selection_posteriors.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
         L.snf_fmllr_accumulate.argtypes = [i32, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, vp, vp]
         L.snf_vtln_gram.argtypes = [i32, vp, vp, vp, i64, i32, vp, vp]
+        L.snf_vtln_gram_rows.argtypes = [i32, vp, vp, vp, vp, vp, i64, i32, vp, vp]
         L.snf_lvtln_select.argtypes = [i32, vp, i64, i32, vp, vp, i32, i32, C.c_double, i32, vp, vp, vp, vp, vp,
                                        vp]
         L.snf_affine_apply_segments.argtypes = [i32, vp, i64, i32, vp, i64, vp, vp, vp]

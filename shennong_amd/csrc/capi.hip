@@ -2009,13 +2009,12 @@ int snf_fmllr_accumulate(int device_id, const float* d_x, int64_t n_frames, int3
   return rc;
 }
 
-int snf_vtln_gram(int device_id, const float* d_x, const float* d_y, const float* d_weights, int64_t n_frames,
-                  int32_t dim, double* d_gram, void* stream) {
-  if (n_frames < 0) return set_error(SNF_E_INVALID, "vtln: number of frames < 0");
-  if (dim < 1 || dim > 64) return set_error(SNF_E_INVALID, "vtln: feature dimension must be in [1, 64]");
-  if (n_frames > 0 && (!d_x || !d_y)) return set_error(SNF_E_INVALID, "vtln: null frames buffer");
-  if (!d_gram) return set_error(SNF_E_INVALID, "vtln: null output buffer");
-  if (n_frames > (int64_t(1) << 28)) return set_error(SNF_E_INVALID, "vtln: frame block too large");
+extern "C++" {
+namespace {
+// The Gram's scratch (records, partials, item and reduction lists) and its one segment's schedule; `records`
+// launches the record pre-pass and the product on what it is given.
+template <typename Launch>
+int vtln_gram_common(int device_id, int64_t n_frames, int32_t dim, double* d_gram, void* stream, Launch records) {
   const int64_t V = 2 * int64_t(dim) + 1, uv = V * V;
   const int64_t off[2] = {0, n_frames};
   std::vector<int64_t> items, red;
@@ -2038,10 +2037,46 @@ int snf_vtln_gram(int device_id, const float* d_x, const float* d_y, const float
     SNF_HIP_CHECK(hipMemcpyAsync(d_items, items.data(), sizeof(int64_t) * items.size(), hipMemcpyHostToDevice, s));
   if (!red.empty())
     SNF_HIP_CHECK(hipMemcpyAsync(d_red, red.data(), sizeof(int64_t) * red.size(), hipMemcpyHostToDevice, s));
-  rc = launch_vtln_gram(d_x, d_y, d_weights, n_frames, dim, rec, d_items, int64_t(items.size() / 3), d_gram, part,
-                        d_red, int64_t(red.size() / 3), s);
+  rc = records(rec, d_items, int64_t(items.size() / 3), part, d_red, int64_t(red.size() / 3), s);
   if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "vtln gram kernels failed");
   return rc;
+}
+
+// `frames`: every frame source is given (checked only when there are frames)
+int vtln_gram_check(int64_t n_frames, int32_t dim, bool frames, const double* d_gram) {
+  if (n_frames < 0) return set_error(SNF_E_INVALID, "vtln: number of frames < 0");
+  if (dim < 1 || dim > 64) return set_error(SNF_E_INVALID, "vtln: feature dimension must be in [1, 64]");
+  if (n_frames > 0 && !frames) return set_error(SNF_E_INVALID, "vtln: null frames buffer");
+  if (!d_gram) return set_error(SNF_E_INVALID, "vtln: null output buffer");
+  if (n_frames > (int64_t(1) << 28)) return set_error(SNF_E_INVALID, "vtln: frame block too large");
+  return SNF_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int snf_vtln_gram(int device_id, const float* d_x, const float* d_y, const float* d_weights, int64_t n_frames,
+                  int32_t dim, double* d_gram, void* stream) {
+  int rc = vtln_gram_check(n_frames, dim, d_x && d_y, d_gram);
+  if (rc) return rc;
+  return vtln_gram_common(device_id, n_frames, dim, d_gram, stream,
+                          [&](double* rec, const int64_t* items, int64_t n_items, double* part, const int64_t* red,
+                              int64_t n_red, hipStream_t s) {
+                            return launch_vtln_gram(d_x, d_y, d_weights, n_frames, dim, rec, items, n_items, d_gram,
+                                                    part, red, n_red, s);
+                          });
+}
+
+int snf_vtln_gram_rows(int device_id, const float* const* d_x_blocks, const float* const* d_y_blocks,
+                       const int32_t* d_block, const int64_t* d_row, const float* d_weights, int64_t n_frames,
+                       int32_t dim, double* d_gram, void* stream) {
+  int rc = vtln_gram_check(n_frames, dim, d_x_blocks && d_y_blocks && d_block && d_row, d_gram);
+  if (rc) return rc;
+  return vtln_gram_common(device_id, n_frames, dim, d_gram, stream,
+                          [&](double* rec, const int64_t* items, int64_t n_items, double* part, const int64_t* red,
+                              int64_t n_red, hipStream_t s) {
+                            return launch_vtln_gram_rows(d_x_blocks, d_y_blocks, d_block, d_row, d_weights, n_frames,
+                                                         dim, rec, items, n_items, d_gram, part, red, n_red, s);
+                          });
 }
 
 int snf_lvtln_select(int device_id, const double* d_stats, int64_t n_segments, int32_t dim, const double* d_A,

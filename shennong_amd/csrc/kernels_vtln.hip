@@ -20,6 +20,8 @@
 // 2. Weighted Gram for the mapping transforms: S = sum_f w_f z_f z_f^T, z = [x | 1 | y] (U = V = 2D+1), one
 //    segment.  Its blocks are every sum of reference vtln.py:299-343 (Q, l, c, beta, sum_xplus, sumsq_x and,
 //    from the diagonals, sumsq_diff).
+//    The Gram's frames are either two compact [F x D] arrays or (snf_vtln_gram_rows) rows gathered from
+//    [rows x D] blocks by a (block, row) list: the same records in the same order, so the same bits.
 //    Both products run through vtln_product_kernel: a pre-pass writes per-frame float64 records (fMLLR:
 //    [x+ | b | a | count], R = 3D+2; Gram: [x | 1 | y | w], R = 2D+2); a workgroup (4 waves) owns 128 rows x
 //    64 columns of S for one ITEM (a run of at most vtln_item_frames() = 2 048 frames of one segment), stages kTileT-frame
@@ -47,8 +49,8 @@
 //   vtln_product_kernel<fmllr|gram>  86 VGPRs + 64 AGPRs (8 f64x4 accumulators per lane), LDS 49 664 B:
 //                                    3 waves/SIMD
 //   lvtln_select_kernel              82 VGPRs, LDS 50 728 B (G_d, K_d, a 32 x 64 fp64 (class, k) table): 3 waves/SIMD
-//   vtln_fmllr_rec_kernel 22, vtln_gram_rec_kernel 13, vtln_reduce_kernel 8, vtln_apply_kernel 13 VGPRs:
-//   8 waves/SIMD
+//   vtln_fmllr_rec_kernel 22, vtln_gram_rec_kernel 13, vtln_gram_rows_rec_kernel 14, vtln_reduce_kernel 8,
+//   vtln_apply_kernel 13 VGPRs: 8 waves/SIMD
 #include <math.h>
 
 #include <algorithm>
@@ -120,6 +122,30 @@ __global__ void __launch_bounds__(kThreads) vtln_gram_rec_kernel(const float* __
   if (d < D) {
     r[d] = static_cast<double>(x[f * D + d]);
     r[D + 1 + d] = static_cast<double>(y[f * D + d]);
+  } else {
+    r[D] = 1.0;
+    r[2 * D + 1] = w ? static_cast<double>(w[f]) : 1.0;
+  }
+}
+
+// Gram over gathered rows: record f takes row row[f] of block blk[f] of both x and y (blocks row-major
+// [rows x D]); the records, hence the product, equal those of the rows gathered into x / y beforehand.
+__global__ void __launch_bounds__(kThreads) vtln_gram_rows_rec_kernel(const float* const* __restrict__ xb,
+                                                                     const float* const* __restrict__ yb,
+                                                                     const int32_t* __restrict__ blk,
+                                                                     const int64_t* __restrict__ row,
+                                                                     const float* __restrict__ w, int64_t F, int D,
+                                                                     double* __restrict__ rec) {
+  const int64_t e = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  const int64_t f = e / (D + 1);
+  const int d = static_cast<int>(e % (D + 1));
+  if (f >= F) return;
+  double* r = rec + f * (2 * D + 2);
+  if (d < D) {
+    const int b = blk[f];
+    const int64_t src = row[f] * D + d;
+    r[d] = static_cast<double>(xb[b][src]);
+    r[D + 1 + d] = static_cast<double>(yb[b][src]);
   } else {
     r[D] = 1.0;
     r[2 * D + 1] = w ? static_cast<double>(w[f]) : 1.0;
@@ -436,6 +462,18 @@ int launch_vtln_gram(const float* x, const float* y, const float* w, int64_t F, 
   if (F > 0) {
     hipLaunchKernelGGL(vtln_gram_rec_kernel, dim3(blocks(F * (D + 1), kThreads)), dim3(kThreads), 0, stream, x, y, w,
                        F, D, rec);
+    SNF_HIP_CHECK(hipGetLastError());
+  }
+  return launch_product<kModeGram>(rec, 2 * D + 2, D, V, V, items, n_items, 1, out, part, red, n_red, stream);
+}
+
+int launch_vtln_gram_rows(const float* const* xb, const float* const* yb, const int32_t* blk, const int64_t* row,
+                          const float* w, int64_t F, int D, double* rec, const int64_t* items, int64_t n_items,
+                          double* out, double* part, const int64_t* red, int64_t n_red, hipStream_t stream) {
+  const int V = 2 * D + 1;
+  if (F > 0) {
+    hipLaunchKernelGGL(vtln_gram_rows_rec_kernel, dim3(blocks(F * (D + 1), kThreads)), dim3(kThreads), 0, stream, xb,
+                       yb, blk, row, w, F, D, rec);
     SNF_HIP_CHECK(hipGetLastError());
   }
   return launch_product<kModeGram>(rec, 2 * D + 2, D, V, V, items, n_items, 1, out, part, red, n_red, stream);

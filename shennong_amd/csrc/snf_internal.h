@@ -372,6 +372,9 @@ int launch_fmllr_accumulate(const float* x, int64_t F, int D, const int32_t* sel
 int launch_vtln_gram(const float* x, const float* y, const float* w, int64_t F, int D, double* rec,
                      const int64_t* items, int64_t n_items, double* out, double* part, const int64_t* red,
                      int64_t n_red, hipStream_t stream);
+int launch_vtln_gram_rows(const float* const* xb, const float* const* yb, const int32_t* blk, const int64_t* row,
+                          const float* w, int64_t F, int D, double* rec, const int64_t* items, int64_t n_items,
+                          double* out, double* part, const int64_t* red, int64_t n_red, hipStream_t stream);
 int launch_lvtln_select(const double* stats, int64_t S, int D, const double* A, const double* logdets, int C,
                         int norm_type, double logdet_scale, int default_class, double* objf, int32_t* cls,
                         double* impr, double* count, float* transform, hipStream_t stream);

@@ -281,6 +281,13 @@ def reduce_named_stats(names, stats, group=None):
     return np.stack([full[index[name]] for name in names]) if len(names) else full[:0]
 
 
+def _refuse_vtln(config):
+    if 'vtln' in config:
+        raise ValueError(
+            'the sharded pipeline does not train VTLN warps from a "vtln" entry: train them once '
+            '(VtlnProcessor.process) and give the precomputed warps instead (warps=...)')
+
+
 def extract_features_sharded(configuration, utterances, warps=None, dst=0, group=None, log=None):
     """``pipeline.extract_features`` over the ranks of one node: every rank passes the same
     `utterances`, works on its length-balanced shard with the device-resident pipeline, and the CMVN
@@ -296,6 +303,7 @@ def extract_features_sharded(configuration, utterances, warps=None, dst=0, group
     transport = _transport(group)
     rank, world = transport.rank, transport.world_size
     config = pipeline._init_config(configuration, log=log)
+    _refuse_vtln(config)
     if warps:
         warps = pipeline._init_warps(warps, config, utterances, log)
     utts = list(utterances)
@@ -409,6 +417,7 @@ def extract_features_streamed_sharded(configuration, utterances, sink, warps=Non
     transport = _transport(group)
     rank, world = transport.rank, transport.world_size
     config = pipeline._init_config(configuration, log=log)
+    _refuse_vtln(config)
     if warps:
         warps = pipeline._init_warps(warps, config, utterances, log)
     utts = list(utterances)

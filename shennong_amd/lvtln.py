@@ -4,8 +4,8 @@
   ``A_c`` [D, D] and one warp per class, a default class, and ``logdets[c] = log|det A_c|`` (float64 here).
 - :class:`FmllrStats` holds Kaldi's ``AffineXformStats``: ``beta``, ``K`` [D, D+1], ``G`` [D, D+1, D+1]
   (float64).
-- The device functions wrap the ``snf_fmllr_accumulate`` / ``snf_vtln_gram`` / ``snf_lvtln_select`` /
-  ``snf_affine_apply_segments`` kernels (``csrc/kernels_vtln.hip``, whose header states the math).
+- The device functions wrap the ``snf_fmllr_accumulate`` / ``snf_vtln_gram`` / ``snf_vtln_gram_rows`` /
+  ``snf_lvtln_select`` / ``snf_affine_apply_segments`` kernels (``csrc/kernels_vtln.hip``, whose header states the math).
 
 Binary layout (Kaldi binary mode, the ``\\0B`` marker first when a whole file), as read from upstream
 ``LinearVtln::Write`` / ``Read`` without a Kaldi build to confirm it::
@@ -229,6 +229,43 @@ def vtln_gram(dx, dy, nframes, dim, dweights=None, device=None):
     out = _backend.DeviceBuffer(8 * V * V, device)
     _backend.check(_backend.lib().snf_vtln_gram(
         out.device, _vp(dx), _vp(dy), _vp(dweights), int(nframes), int(dim), _vp(out), None))
+    return out.download(np.empty((V, V), np.float64))
+
+
+def upload_row_list(block, row, device=None):
+    """The (block, row) list of :func:`vtln_gram_rows` in HBM: (DeviceBuffer int32 [F], DeviceBuffer int64 [F])"""
+    block = np.ascontiguousarray(block, dtype=np.int32)
+    row = np.ascontiguousarray(row, dtype=np.int64)
+    if block.shape != row.shape or block.ndim != 1:
+        raise ValueError('block and row lists must be 1-D and of the same length')
+    dblock = _backend.DeviceBuffer(block.nbytes, device)
+    drow = _backend.DeviceBuffer(row.nbytes, dblock.device)
+    if block.size:
+        dblock.upload(block)
+        drow.upload(row)
+    return dblock, drow
+
+
+def vtln_gram_rows(x_blocks, y_blocks, dblock, drow, nframes, dim, dweights=None):
+    """:func:`vtln_gram` over rows gathered on the device: frame f is row ``row[f]`` of block ``block[f]`` of
+    `x_blocks` and of `y_blocks` (lists of DeviceBuffers [rows, D] float32, same shapes in both lists;
+    ``dblock`` / ``drow`` from :func:`upload_row_list`, every pair in range - the caller checks it).  Bit for
+    bit what vtln_gram gives on the rows gathered on the host, in the same order."""
+    if len(x_blocks) != len(y_blocks) or not x_blocks:
+        raise ValueError('x and y need the same, non-zero number of blocks')
+    V = 2 * dim + 1
+    device = x_blocks[0].device
+    out = _backend.DeviceBuffer(8 * V * V, device)
+    pointers = []
+    for blocks in (x_blocks, y_blocks):
+        table = np.asarray([b.ptr for b in blocks], dtype=np.uint64)
+        pointers.append(_backend.DeviceBuffer(table.nbytes, device))
+        pointers[-1].upload(table)
+    _backend.check(_backend.lib().snf_vtln_gram_rows(
+        device, _vp(pointers[0]), _vp(pointers[1]), _vp(dblock), _vp(drow), _vp(dweights), int(nframes),
+        int(dim), _vp(out), None))
+    for table in pointers:
+        table.free(synced=True)
     return out.download(np.empty((V, V), np.float64))
 
 

@@ -9,11 +9,16 @@ utterances instead of a per-utterance thread pool:
     features (+ VTLN warps) -> [energy -> VAD -> CMVN statistics per speaker / utterance]
     -> [pitch -> pitch post-processing] -> CMVN apply -> delta -> pitch concatenation (tolerance 2)
 
-Not provided by this pipeline: VTLN training through the configuration (`with_vtln`, the 'vtln' entry),
-CREPE pitch, bottleneck features.  VTLN training itself is available as
-:class:`~shennong_amd.processor.vtln.VtlnProcessor` (over the
-:class:`~shennong_amd.processor.ubm.DiagUbmProcessor` UBM); give the warps its ``process`` returns to
-:func:`extract_features` (``warps=...``).
+A 'vtln' entry in the configuration (the parameters of
+:class:`~shennong_amd.processor.vtln.VtlnProcessor`, as the reference's ``get_default_config(with_vtln=...)``
+writes them, the "simple" shape with ``features: default`` included) trains the warps on the utterances first
+- once, with ``VtlnProcessor(**config['vtln']).process(utterances)`` - and then extracts with them: the result
+is that of :func:`extract_features` without the entry and with ``warps=`` those warps.  Precomputed warps can
+be given instead (``warps=...``), not both.  ``get_default_config(with_vtln=...)`` does not write the entry
+here; build it as ``config['vtln'] = VtlnProcessor().get_params()``.  The sharded entry points
+(:mod:`shennong_amd.distributed`) take precomputed warps only.
+
+Not provided by this pipeline: CREPE pitch, bottleneck features.
 """
 
 import os
@@ -72,11 +77,15 @@ def get_default_config(features, to_yaml=False, yaml_commented=True,
     values, `sample_rate` and `htk_compat` filtered out of the features entry, frame parameters
     filtered out of the pitch entry).
 
+    `with_vtln` is refused here.  The pipeline itself does train VTLN warps from a 'vtln' entry: add one to
+    the returned configuration as ``config['vtln'] = VtlnProcessor().get_params()`` (or with
+    ``features: default`` and ``ubm: {features: default, ...}``, the reference's "simple" shape).
+
     Raises
     ------
     ValueError
         If `features` is not in :func:`valid_features`, or if `with_pitch` / `with_vtln` ask for
-        something this backend does not provide ('crepe', VTLN training).
+        something this backend does not provide ('crepe', a 'vtln' entry written by this function).
     """
     if features not in valid_features():
         raise ValueError('invalid features "{}", must be in {}'.format(
@@ -223,12 +232,8 @@ def _init_config(config, log=get_logger('pipeline', 'warning')):
             '(must have one and only one entry of {}): {}'
             .format(', '.join(valid_features()), ', '.join(features)))
 
-    if 'vtln' in config:
-        if features[0] == 'spectrogram':
-            raise ValueError(f'{features[0]} features do not support VTLN')
-        raise ValueError(
-            'VTLN training is not available in this backend '
-            '(give precomputed warps to extract_features instead)')
+    if 'vtln' in config and features[0] == 'spectrogram':
+        raise ValueError(f'{features[0]} features do not support VTLN')
 
     if 'cmvn' in config:
         if 'by_speaker' not in config['cmvn']:
@@ -254,6 +259,9 @@ def _init_config(config, log=get_logger('pipeline', 'warning')):
         msg.append('cmvn by {}{}'.format(
             'speaker' if config['cmvn']['by_speaker'] else 'utterance',
             ' with vad' if config['cmvn']['with_vad'] else ''))
+    if 'vtln' in config:
+        msg.append('vtln by {}'.format(
+            'speaker' if config['vtln'].get('by_speaker', True) else 'utterance'))
     log.info(
         'pipeline configured for %s features extraction%s',
         features[0], ' with {}'.format(', '.join(msg)) if msg else '')
@@ -266,7 +274,7 @@ def _init_warps(warps, config, utterances, log):
     features = [k for k in config.keys() if k in valid_features()][0]
     if features == 'spectrogram':
         raise ValueError(f'{features} features do not support VTLN')
-    if 'vtln' in config:  # pragma: nocover (rejected by _init_config)
+    if 'vtln' in config:
         raise ValueError(
             'warps are given but "vtln" processor already defined '
             'in the configuration')
@@ -282,6 +290,24 @@ def _init_warps(warps, config, utterances, log):
     return {name: float(warp) for name, warp in warps.items()}
 
 
+def _train_vtln(config, utterances, warps, njobs, log):
+    """(warps, configuration) to extract with: for a configuration with a 'vtln' entry, the per-utterance warps
+    that ``VtlnProcessor(**config['vtln']).process(utterances)`` trains (once) and the configuration without the
+    entry (reference pipeline.py:534-539); any other configuration passes through"""
+    if 'vtln' not in config:
+        return warps, config
+    if warps:
+        raise ValueError(
+            'warps are given but "vtln" processor already defined '
+            'in the configuration')
+    from shennong_amd.processor.vtln import VtlnProcessor
+    proc = VtlnProcessor(**config['vtln'])
+    proc.log.setLevel(log.getEffectiveLevel())
+    log.info('training VTLN warps')
+    warps = proc.process(utterances, njobs=njobs)
+    return warps, {k: v for k, v in config.items() if k != 'vtln'}
+
+
 def extract_features(configuration, utterances, warps=None, njobs=1,
                      log=get_logger('pipeline', 'warning')):
     """Speech features extraction pipeline
@@ -294,7 +320,8 @@ def extract_features(configuration, utterances, warps=None, njobs=1,
     utterances : :class:`~shennong_amd.utterances.Utterances`
         The utterances to extract the features on.
     warps : dict, optional
-        Precomputed VTLN warps (str: float) indexed by utterance name or by speaker.
+        Precomputed VTLN warps (str: float) indexed by utterance name or by speaker.  Not together with a
+        'vtln' entry in the configuration, which trains the warps on `utterances` first.
     njobs : int, optional
         Validated like the reference; the work itself is batched on the GPU.
 
@@ -305,12 +332,14 @@ def extract_features(configuration, utterances, warps=None, njobs=1,
     Raises
     ------
     ValueError
-        If the configuration, the utterances or the warps are invalid.
+        If the configuration, the utterances or the warps are invalid, or if both `warps` and a 'vtln' entry
+        are given.
     """
     get_njobs(njobs, log=log)
     config = _init_config(configuration, log=log)
     log.info('detected format for utterances index is: %s',
              utterances.format(type=str))
+    warps, config = _train_vtln(config, utterances, warps, njobs, log)
     if _too_large_for_one_batch(utterances):
         # the corpus in one launch per stage would not fit the HBM that is free (the pitch tracker alone keeps
         # 2.3 GB of scratch per hour of audio): the same features - bit for bit, see extract_features_streamed -
@@ -507,11 +536,15 @@ def extract_features_streamed(configuration, utterances, sink, warps=None,
     conversion, check or gather (what bounded this function before round 6: the host, not the link).
     `stats` (a :class:`RunStats`): link bytes, transfer waits and kernel milliseconds summed over the run.
 
+    A 'vtln' entry in the configuration trains the warps on the whole of `utterances` first (see
+    :func:`extract_features`), then the batches are extracted with them.
+
     Returns the number of utterances written."""
     depth = min(get_njobs(njobs, log=log), 8)
     config = _init_config(configuration, log=log)
     if max_batch_duration is not None and not max_batch_duration > 0:
         raise ValueError('max_batch_duration must be strictly positive')
+    warps, config = _train_vtln(config, utterances, warps, njobs, log)
     if warps:
         warps = _init_warps(warps, config, utterances, log)
     by_speaker = 'cmvn' in config and config['cmvn']['by_speaker']
@@ -690,6 +723,8 @@ class _ResidentWaves:
     """Uploaded waveforms kept in HBM between the two passes of :func:`extract_features_streamed`
     (96 kB per 3 s utterance: 16 GiB hold 140 hours of 16 kHz audio), so that the second pass neither reads
     the audio files nor crosses the host link again.  Batches that do not fit the budget are re-uploaded."""
+    every_pass = False   # (True: a pass that is not a statistics pass offers its blocks too, see _SweepWaves)
+
     def __init__(self, budget):
         self.budget = int(budget)
         self.held = 0
@@ -742,6 +777,36 @@ class _ResidentWaves:
                 pass
         for d_wave, _ in items:
             d_wave.free(synced=True)
+
+
+class _Borrowed:
+    """A device block lent to a pass by a _SweepWaves: the pass uses it like its own, its free() gives nothing back"""
+    def __init__(self, block):
+        self.ptr, self.nbytes, self.device = block.ptr, block.nbytes, block.device
+
+    def free(self, synced=False):
+        pass
+
+
+class _SweepWaves(_ResidentWaves):
+    """Uploaded waveforms kept in HBM for EVERY later pass over the same utterances (the mapping sweep of
+    VtlnProcessor: the unwarped extraction and one warped extraction per class from ONE upload).  The first
+    pass offers its blocks (any pass, not only a statistics pass: `every_pass`); the later ones borrow them
+    (:class:`_Borrowed`) instead of taking them; clear() frees them."""
+    every_pass = True
+
+    def __init__(self):
+        super().__init__(1 << 62)
+
+    def offer(self, key, d_wave, soff):
+        if self.holds(key):   # (a borrowed block coming back)
+            return False
+        return super().offer(key, d_wave, soff)
+
+    def take(self, key):
+        with self._lock:
+            item = self._items.get(key)
+        return None if item is None else (_Borrowed(item[0]), item[1])
 
 
 class _BatchView:
@@ -958,14 +1023,17 @@ def _classes_of(*keys):
 
 def _extract_features(config, utterances, warps, log, tolerance=2, stats_hook=None,
                       stats_only=False, resident=None, batch_id=None, device_out=None, stats=None,
-                      stages=None, utterance_properties=True, defer=False):
+                      stages=None, utterance_properties=True, defer=False, bare=False):
     """`defer`: return ``(features, finish)`` with the copy of the result block still on its way; `finish()`
     waits for it and must be called before the data are read (extract_features_streamed: the copy of batch k
-    crosses the link beside the launches of batch k + 1)"""
+    crosses the link beside the launches of batch k + 1).  `bare` (with `device_out`): no Features are made;
+    returns the frame offsets [utterances + 1] of every block appended to `device_out`, in the same order
+    (the mapping sweep of VtlnProcessor reads nothing else)"""
     from shennong_amd.utils import paused_gc
     with paused_gc():   # (thousands of small objects per batch, none of them garbage: see utils.paused_gc)
         run = _PipelineRun(config, utterances, warps, log, tolerance, resident, batch_id, stats, stages,
                            utterance_properties)
+        run.bare = bare and device_out is not None
         try:
             return run.execute(stats_hook, stats_only, device_out, defer)
         except BaseException:
@@ -1017,6 +1085,7 @@ class _PipelineRun:
         self.pclasses, self.pcls_of = [], np.zeros(self.n, dtype=np.int64)   # the same for the pitch features
         self.rate_of = [None] * self.n
         self.frame_length = self.frame_shift = None
+        self.bare = False     # (see _extract_features)
 
     def abort(self):
         for group in self.groups:
@@ -1043,10 +1112,10 @@ class _PipelineRun:
                 self.stage_vad(group)
             if group.pitch_job is not None:
                 pass   # (the tracker still reads the audio: released where it is waited for, stage_join)
-            elif stats_only and self.resident is not None and self.resident.offer(
+            elif self.resident is not None and (stats_only or self.resident.every_pass) and self.resident.offer(
                     (self.batch_id, group.rate), group.blocks['wave'], group.soff):
                 block = group.give('wave')
-                if self.with_pitch and _TRACK_IN_FIRST_PASS:
+                if stats_only and self.with_pitch and _TRACK_IN_FIRST_PASS:
                     # the tracker of this batch starts NOW, on the audio that stays in HBM: the first pass waits
                     # for uploads, the second for downloads - the GPU is idle in the first
                     self.resident.offer_track(
@@ -1327,6 +1396,7 @@ class _PipelineRun:
         utts, n, cache, log, tolerance = self.utts, self.n, self.cache, self.log, self.tolerance
         results = [None] * n
         pending = []
+        block_offsets = []    # (bare runs)
         for group in self.groups:
             idx = group.idx
             if group.pitch_job is not None:
@@ -1374,6 +1444,9 @@ class _PipelineRun:
                 if host.size:
                     _backend.check_finite_device(group.ptr('feat'), host.size)
                 device_out.append((group.give('feat'), [utts[i].name for i in idx.tolist()], group.dim))
+                if self.bare:
+                    block_offsets.append(group.foff)
+                    continue
             else:
                 host = _backend.result_array((rows, group.dim), np.float32)
                 if host.size:
@@ -1390,6 +1463,9 @@ class _PipelineRun:
             else:
                 for i, a, b in zip(idx.tolist(), cuts, cuts[1:]):
                     results[i] = host[a:b]
+        if self.bare:
+            self._count(batches=1, utterances=n)
+            return block_offsets
         # what is this utterance's own (its audio, its speaker) is made when its properties are first read; the
         # processors' part of the properties and the times are shared by every utterance with the same history /
         # frame count and copied when first read (Features._of_batch).  Times are generated, hence sorted; the

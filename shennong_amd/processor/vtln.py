@@ -20,7 +20,13 @@ Examples
 >>> warps = vtln.process(utterances)                          # doctest: +SKIP
 
 The warps go to ``extract_features(config, utterances, warps=warps)`` or to a processor's ``process(...,
-vtln_warp=...)``.  ``get_default_config(with_vtln=...)`` is not wired to this class.
+vtln_warp=...)``.  A ``vtln`` entry in the pipeline configuration (``config['vtln'] = VtlnProcessor().get_params()``)
+has ``extract_features`` train them with this class and extract with them.
+
+The mapping transforms take one warped extraction per class.  When the corpus fits one device batch, they run
+as a device-resident sweep (:meth:`VtlnProcessor._mapping_sweep`): the audio goes up once, every class's
+features stay in HBM and the Grams gather their rows there.  The results are bit for bit those of the host
+round trip, which larger corpora keep.
 
 Divergences from the reference
 ------------------------------
@@ -49,6 +55,7 @@ from shennong_amd.logger import null_logger
 from shennong_amd.postprocessor.cmvn import SlidingWindowCmvnPostProcessor
 from shennong_amd.postprocessor.vad import VadPostProcessor
 from shennong_amd.processor.ubm import DiagUbmProcessor
+from shennong_amd.utils import get_njobs
 
 
 def mapping_from_gram(M, dim):
@@ -73,6 +80,28 @@ def mapping_from_gram(M, dim):
     scale = np.sqrt(x_var / y_var)
     A = (W[:, :D] * scale[:, None]).astype(np.float32)
     return A, (error, sumsq_diff / beta, sumsq_x / beta)
+
+
+def _sweep_on_device(utterances):
+    """True when the mapping transforms take the device-resident sweep (the audio, every class's features and
+    the row list stay in HBM); False - a corpus that does not fit one device batch - keeps the per-class host
+    round trip (extract_features_warp, trim, subsample, upload)"""
+    return not pipeline._too_large_for_one_batch(utterances)
+
+
+def sweep_rows(names, vad, subsample, layout):
+    """The records of the mapping Gram as (block [F] int32, row [F] int64): per utterance of `names` in order,
+    ``np.flatnonzero(vad[u])[::subsample]`` - the rows ``FeaturesCollection.trim(vad)`` then ``[::subsample]``
+    keeps - offset to where the frames of u start in its block, ``layout[u] = (block, first row)``"""
+    blocks, rows = [], []
+    for name in names:
+        block, first = layout[name]
+        keep = np.flatnonzero(vad[name])[::subsample]
+        rows.append(keep + first)
+        blocks.append(np.full(keep.size, block, dtype=np.int32))
+    if not rows:
+        return np.zeros(0, np.int32), np.zeros(0, np.int64)
+    return np.concatenate(blocks).astype(np.int32), np.concatenate(rows).astype(np.int64)
 
 
 class VtlnProcessor(BaseProcessor):
@@ -302,8 +331,10 @@ class VtlnProcessor(BaseProcessor):
         self._mapping_from_device(dx, dy, dw, nframes, class_idx, warp)
 
     def _mapping_from_device(self, dx, dy, dw, nframes, class_idx, warp):
+        self._mapping_from_gram(_lvtln.vtln_gram(dx, dy, nframes, self.lvtln.dim(), dw), class_idx, warp)
+
+    def _mapping_from_gram(self, M, class_idx, warp):
         dim = self.lvtln.dim()
-        M = _lvtln.vtln_gram(dx, dy, nframes, dim, dw)
         A, (error, sqdiff, scatter) = mapping_from_gram(M, dim)
         for i in range(dim):
             self.log.debug(
@@ -424,6 +455,126 @@ class VtlnProcessor(BaseProcessor):
         self.log.debug(message)
         return transforms, warps, all_trans
 
+    # ---- base transforms (reference vtln.py:553-610)
+    def _base_transforms(self, utterances, ubm, num_classes, njobs=1, stats=None):
+        """Features with the sliding CMVN popped, VAD on the raw features, CMVN, trim and subsample: returns the
+        original frames.  Sets the mapping transform of every class on the way: one warped extraction per
+        class, on the device (:meth:`_mapping_sweep`) unless the corpus does not fit one device batch.
+        `stats` (a pipeline.RunStats) counts the link bytes and kernel time of the device sweep."""
+        cmvn_config = self.features.pop('sliding_window_cmvn', None)
+        waves = None
+        try:
+            if _sweep_on_device(utterances):
+                # the unwarped pass keeps its audio in HBM for the warped ones
+                get_njobs(njobs, log=null_logger())
+                config = pipeline._init_config(self.features, log=null_logger())
+                waves = pipeline._SweepWaves()
+                raw_mfcc = pipeline._extract_features(config, pipeline._view_of(utterances), None, null_logger(),
+                                                      resident=waves, stats=stats)
+            else:
+                raw_mfcc = pipeline.extract_features(self.features, utterances, njobs=njobs, log=null_logger())
+            self.log.debug('... computing VAD decision')
+            utts = list(raw_mfcc.keys())
+            decisions = VadPostProcessor(**ubm.vad)._process_batch([raw_mfcc[u] for u in utts])
+            vad = {u: d.data.reshape((d.shape[0],)).astype(bool) for u, d in zip(utts, decisions)}
+            if cmvn_config is not None:
+                normed = SlidingWindowCmvnPostProcessor(**cmvn_config)._process_batch([raw_mfcc[u] for u in utts])
+                orig_features = FeaturesCollection(zip(utts, normed))
+            else:
+                orig_features = raw_mfcc
+            orig_features = orig_features.trim(vad)
+            orig_features = FeaturesCollection(
+                {utt: feats.copy(subsample=self.subsample) for utt, feats in orig_features.items()})
+
+            if waves is not None:
+                self._mapping_sweep(config, utterances, raw_mfcc, vad, num_classes, waves, stats)
+            else:
+                self._mapping_host(utterances, utts, vad, num_classes, njobs)
+        finally:
+            if waves is not None:
+                waves.clear()
+            if cmvn_config is not None:
+                self.features['sliding_window_cmvn'] = cmvn_config
+        return orig_features
+
+    def _mapping_host(self, utterances, utts, vad, num_classes, njobs):
+        """The base transforms with a host round trip per class: the unwarped frames uploaded once, one warped
+        extraction per class downloaded, trimmed, subsampled and uploaded"""
+        dim = self.lvtln.dim()
+        featsub_unwarped = pipeline.extract_features(
+            self.features, utterances, njobs=njobs, log=null_logger()).trim(vad)
+        xs = [featsub_unwarped[u].data[::self.subsample] for u in utts]
+        nframes = sum(x.shape[0] for x in xs)
+        dx = _backend.upload_rows(xs, np.float32)
+        del featsub_unwarped
+        for c in range(num_classes):
+            this_warp = self.min_warp + c * self.warp_step
+            self.log.info('Computing base transform (warp=%s) %s/%s', this_warp, c + 1, num_classes)
+            warped = pipeline.extract_features_warp(
+                self.features, utterances, this_warp, null_logger(), njobs=njobs).trim(vad)
+            ys = [warped[u].data[::self.subsample] for u in utts]
+            for x, y in zip(xs, ys):
+                if x.shape != y.shape:
+                    raise ValueError('Number of rows and/or columns differs: '
+                                     f'{x.shape[0]} vs {y.shape[0]} rows, {x.shape[1]} vs '
+                                     f'{y.shape[1]} columns, {dim} dim')
+            dy = _backend.upload_rows(ys, np.float32)
+            self._mapping_from_device(dx, dy, None, nframes, c, this_warp)
+
+    def _mapping_sweep(self, config, utterances, raw_mfcc, vad, num_classes, waves, stats=None):
+        """The base transforms from data that stay in HBM: every warped pass borrows the audio the unwarped one
+        left in `waves` and leaves its features in HBM (one block per sample rate); the unwarped rows go up once,
+        in the same layout, and the Gram of every class gathers its records from both by one (block, row) list -
+        the rows the host path trims and subsamples, in the same order: the same Gram, bit for bit."""
+        dim = self.lvtln.dim()
+        view = pipeline._view_of(utterances)
+        names = list(raw_mfcc.keys())
+        xdim = raw_mfcc[names[0]].ndims if names else dim
+        x_blocks, row_list, layout, counts = [], None, None, None
+        try:
+            for c in range(num_classes):
+                this_warp = self.min_warp + c * self.warp_step
+                self.log.info('Computing base transform (warp=%s) %s/%s', this_warp, c + 1, num_classes)
+                out = []
+                try:
+                    offsets = pipeline._extract_features(
+                        config, view, {u.name: float(this_warp) for u in view}, null_logger(), stages=('delta',),
+                        utterance_properties=False, device_out=out, resident=waves, stats=stats, bare=True)
+                    if layout is None:
+                        # frame counts do not depend on the warp: the layout, the row list and the unwarped
+                        # blocks are made once
+                        layout, counts = {}, {}
+                        for b, ((_, block_names, _), off) in enumerate(zip(out, offsets)):
+                            for i, name in enumerate(block_names):
+                                layout[name] = (b, int(off[i]))
+                                counts[name] = int(off[i + 1] - off[i])
+                        for name in names:
+                            nx, ny = raw_mfcc[name].nframes, counts[name]
+                            if nx != ny or xdim != dim:
+                                raise ValueError('Number of rows and/or columns differs: '
+                                                 f'{nx} vs {ny} rows, {xdim} vs {out[layout[name][0]][2]} '
+                                                 f'columns, {dim} dim')
+                        x_blocks = [_backend.upload_rows([raw_mfcc[n].data for n in block_names], np.float32)
+                                    for _, block_names, _ in out]
+                        blocks_of, rows = sweep_rows(names, vad, self.subsample, layout)
+                        nframes = rows.size
+                        row_list = _lvtln.upload_row_list(blocks_of, rows)
+                    elif any(not np.array_equal(np.diff(off), [counts[n] for n in block_names])
+                             for (_, block_names, _), off in zip(out, offsets)):
+                        raise ValueError('Number of rows and/or columns differs between warps')
+                    if any(ydim != xdim for _, _, ydim in out):
+                        raise ValueError('Number of rows and/or columns differs: '
+                                         f'{xdim} vs {out[0][2]} columns, {dim} dim')
+                    M = _lvtln.vtln_gram_rows(x_blocks, [block for block, _, _ in out], row_list[0], row_list[1],
+                                              nframes, dim)
+                finally:
+                    for block, _, _ in out:
+                        block.free()
+                self._mapping_from_gram(M, c, this_warp)
+        finally:
+            for block in x_blocks + list(row_list or ()):
+                block.free()
+
     # ---- training (reference vtln.py:511-680)
     def process(self, utterances, ubm=None, group_by='utterance', njobs=1):
         """Compute the VTLN warp factors for the given utterances.
@@ -471,46 +622,7 @@ class VtlnProcessor(BaseProcessor):
         default_class = int(0.5 + (1 - self.min_warp) / self.warp_step)
         self.lvtln = _lvtln.LinearVtln(dim, num_classes, default_class)
 
-        cmvn_config = self.features.pop('sliding_window_cmvn', None)
-        try:
-            raw_mfcc = pipeline.extract_features(self.features, utterances, njobs=njobs, log=null_logger())
-            self.log.debug('... computing VAD decision')
-            utts = list(raw_mfcc.keys())
-            decisions = VadPostProcessor(**ubm.vad)._process_batch([raw_mfcc[u] for u in utts])
-            vad = {u: d.data.reshape((d.shape[0],)).astype(bool) for u, d in zip(utts, decisions)}
-            if cmvn_config is not None:
-                normed = SlidingWindowCmvnPostProcessor(**cmvn_config)._process_batch([raw_mfcc[u] for u in utts])
-                orig_features = FeaturesCollection(zip(utts, normed))
-            else:
-                orig_features = raw_mfcc
-            orig_features = orig_features.trim(vad)
-            orig_features = FeaturesCollection(
-                {utt: feats.copy(subsample=self.subsample) for utt, feats in orig_features.items()})
-
-            # base transforms: the unwarped frames uploaded once, one warped extraction per class
-            featsub_unwarped = pipeline.extract_features(
-                self.features, utterances, njobs=njobs, log=null_logger()).trim(vad)
-            xs = [featsub_unwarped[u].data[::self.subsample] for u in utts]
-            nframes = sum(x.shape[0] for x in xs)
-            dx = _backend.upload_rows(xs, np.float32)
-            del featsub_unwarped
-            for c in range(num_classes):
-                this_warp = self.min_warp + c * self.warp_step
-                self.log.info('Computing base transform (warp=%s) %s/%s', this_warp, c + 1, num_classes)
-                warped = pipeline.extract_features_warp(
-                    self.features, utterances, this_warp, null_logger(), njobs=njobs).trim(vad)
-                ys = [warped[u].data[::self.subsample] for u in utts]
-                for x, y in zip(xs, ys):
-                    if x.shape != y.shape:
-                        raise ValueError('Number of rows and/or columns differs: '
-                                         f'{x.shape[0]} vs {y.shape[0]} rows, {x.shape[1]} vs '
-                                         f'{y.shape[1]} columns, {dim} dim')
-                dy = _backend.upload_rows(ys, np.float32)
-                self._mapping_from_device(dx, dy, None, nframes, c, this_warp)
-            del dx, vad
-        finally:
-            if cmvn_config is not None:
-                self.features['sliding_window_cmvn'] = cmvn_config
+        orig_features = self._base_transforms(utterances, ubm, num_classes, njobs)
 
         self.log.debug('Computing Gaussian selection info')
         ubm.gaussian_selection(orig_features)
