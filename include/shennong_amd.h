@@ -424,6 +424,52 @@ int snf_affine_apply_segments(int device_id, const float* d_x, int64_t n_frames,
                               const int64_t* h_seg_offsets, int64_t n_segments, const float* d_transforms,
                               float* d_y, void* stream);
 
+/* ---- bottleneck features (reference processor/bottleneck.py, BottleneckProcessor) ----------------
+ * The BUT/Phonexia extractor on 8 kHz int16 audio: frames of 200 samples every 80, n < 200 ? 0 :
+ * (n - 200) / 80 + 1 of them per utterance.  Batch first: h_*_offsets[n_utts + 1] are HOST int64 tables
+ * (non-decreasing, first 0) of samples, frames or rows per utterance; every other buffer is on the device.
+ * float32 arithmetic except the VAD statistics (float64) and the voiced mean (float64 sums), every sum in
+ * a fixed order (no atomics): an utterance gives the same bits alone and in any batch.  `stream` NULL: the
+ * calling thread's own stream; every call waits for its stream before returning.  Invalid arguments return
+ * SNF_E_INVALID before any device work.
+ */
+/* d_y[m x n] = act(d_x[m x k] d_w[k x n] + d_b[n]), row-major float32, act 0 = identity, 1 = logistic sigmoid
+ * (reference bottleneck.py:461-462 _sigmoid_fun and the `f(Y.dot(W) + b)` of :485-500), on the FP32 matrix
+ * cores: every element is one fused multiply-add chain over k ascending, independent of m. */
+int snf_dense_layer(int device_id, const float* d_x, int64_t m, int32_t k, const float* d_w, const float* d_b,
+                    int32_t n, int32_t act, float* d_y, void* stream);
+/* Voice activity detection (reference bottleneck.py:403-453 _compute_vad with bugfix = False: int16-wrapped
+ * squares, per-frame integer sums, standardisation and 5 EM passes of a 1-D 3-component GMM in float64):
+ * d_mask[total_frames] uint8 (1 = voiced: posterior of component 0 below 0.3), d_voiced[n_utts] int32 the
+ * voiced count.  Where the reference catches a RuntimeWarning (constant signal, an emptied or collapsed
+ * component) the mask is all 0. */
+int snf_bottleneck_vad(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                       uint8_t* d_mask, int32_t* d_voiced, void* stream);
+/* HTK log-mel filterbank (reference bottleneck.py:117-118 _add_dither, :182-217 _fbank_htk): uniform dither
+ * `dither` * U(-1, 1) per sample (keyed by the utterance's content, the sample index and `seed`; 0 = none,
+ * exact), window, 256-point transform, power, 24 filters, log(max(1, .)): d_logmel[total_frames x 24].
+ * d_tables (8-byte aligned float32, built by the host): window[200] | exp(-2 pi i j / 256) as (re, im),
+ * j < 256 | filterbank[129 x 24] row-major (the matrix of bottleneck.py:135-179 _mel_fbank_mx). */
+int snf_bottleneck_fbank(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                         const float* d_tables, float dither, uint64_t seed, float* d_logmel, void* stream);
+/* Network input (reference bottleneck.py:743-754 and :465-474 _preprocess_nn_input): the mean over the voiced
+ * frames is subtracted (0 for an utterance without voiced frames), the first and the last frame repeated 15
+ * times, and every window of 2 context + 1 frames projected per band on the 6 columns of d_basis
+ * [(2 context + 1) x 6]: d_x[rows x 144] band-major, frames + 30 - 2 context rows per utterance
+ * (context <= 64; every utterance needs at least one frame and one row). */
+int snf_bottleneck_nn_input(int device_id, const float* d_logmel, const uint8_t* d_mask, const int32_t* d_voiced,
+                            const int64_t* h_frame_offsets, int64_t n_utts, int32_t context, const float* d_basis,
+                            float* d_x, void* stream);
+/* The two stacked networks (reference bottleneck.py:477-501 _create_nn_extract_st_BN, bn_position 2) with
+ * the input and bottleneck normalisations folded into the first layer of each: h_params[12] HOST array of
+ * DEVICE pointers W1 b1 W2 b2 W3 b3 W5 b5 W6 b6 W7 b7 with W1[144 x w0], W2[w0 x w1], W3[w1 x 80],
+ * W5[400 x w2], W6[w2 x w3], W7[w3 x 80], h_widths = {w0, w1, w2, w3}.  d_bn[rows x 80] receives the first
+ * stage; rows t, t + 5, ..., t + 20 of one utterance are read from it as the 400 inputs of W5 (never written
+ * out as a matrix); d_out[(rows - 20 n_utts) x 80].  Every utterance needs more than 20 rows. */
+int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
+                           const int32_t* h_widths, const float* const* h_params, float* d_bn, float* d_out,
+                           void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

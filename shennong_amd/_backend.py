@@ -42,7 +42,8 @@ EXPORTS = [
     'snf_stream_wait_event', 'snf_stream_query', 'snf_event_synchronize', 'snf_wav_scan', 'snf_wav_read_pcm16',
     'snf_gmm_loglikes', 'snf_gmm_accumulate', 'snf_gmm_gselect', 'snf_gmm_gselect_preselect',
     'snf_gmm_selection_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
-    'snf_affine_apply_segments', 'snf_vtln_gram_rows']
+    'snf_affine_apply_segments', 'snf_vtln_gram_rows', 'snf_dense_layer', 'snf_bottleneck_vad',
+    'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -165,6 +166,11 @@ def lib():
         L.snf_lvtln_select.argtypes = [i32, vp, i64, i32, vp, vp, i32, i32, C.c_double, i32, vp, vp, vp, vp, vp,
                                        vp]
         L.snf_affine_apply_segments.argtypes = [i32, vp, i64, i32, vp, i64, vp, vp, vp]
+        L.snf_dense_layer.argtypes = [i32, vp, i64, i32, vp, vp, i32, i32, vp, vp]
+        L.snf_bottleneck_vad.argtypes = [i32, vp, pi64, i64, vp, vp, vp]
+        L.snf_bottleneck_fbank.argtypes = [i32, vp, pi64, i64, vp, f32, C.c_uint64, vp, vp]
+        L.snf_bottleneck_nn_input.argtypes = [i32, vp, vp, vp, pi64, i64, i32, vp, vp, vp]
+        L.snf_bottleneck_forward.argtypes = [i32, vp, pi64, i64, pi32, C.POINTER(vp), vp, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)

@@ -2125,6 +2125,196 @@ int snf_affine_apply_segments(int device_id, const float* d_x, int64_t n_frames,
   return rc;
 }
 
+// ---- bottleneck extractor (kernels_bottleneck.hip) ------------------------------------------------------
+namespace {
+constexpr int kBnWin = 200, kBnShift = 80, kBnMel = 24, kBnIn = 144, kBnOut = 80, kBnEdge = 15, kBnStack = 5,
+              kBnStackStep = 5;
+
+int bn_check_offsets(const int64_t* h_off, int64_t n, const char* what) {
+  if (n < 0) return set_error(SNF_E_INVALID, std::string("bottleneck: number of utterances < 0"));
+  if (!h_off) return set_error(SNF_E_INVALID, std::string("bottleneck: null ") + what + " offsets table");
+  if (h_off[0] != 0) return set_error(SNF_E_INVALID, std::string("bottleneck: ") + what + " offsets must start at 0");
+  for (int64_t u = 0; u < n; ++u)
+    if (h_off[u + 1] < h_off[u])
+      return set_error(SNF_E_INVALID, std::string("bottleneck: ") + what + " offsets must not decrease");
+  if (h_off[n] > (int64_t(1) << 40)) return set_error(SNF_E_INVALID, "bottleneck: batch too large");
+  return SNF_OK;
+}
+
+int64_t bn_frames(int64_t n) { return n < kBnWin ? 0 : (n - kBnWin) / kBnShift + 1; }
+
+// frame offsets of a waveform batch, [n_utts + 1]
+void bn_frame_offsets(const int64_t* h_soff, int64_t n_utts, std::vector<int64_t>* foff) {
+  foff->assign(n_utts + 1, 0);
+  for (int64_t u = 0; u < n_utts; ++u) (*foff)[u + 1] = (*foff)[u] + bn_frames(h_soff[u + 1] - h_soff[u]);
+}
+}  // namespace
+
+int snf_dense_layer(int device_id, const float* d_x, int64_t m, int32_t k, const float* d_w, const float* d_b,
+                    int32_t n, int32_t act, float* d_y, void* stream) {
+  if (m < 0) return set_error(SNF_E_INVALID, "dense layer: number of rows < 0");
+  if (k < 1 || n < 1) return set_error(SNF_E_INVALID, "dense layer: k and n must be at least 1");
+  if (act != 0 && act != 1) return set_error(SNF_E_INVALID, "dense layer: act must be 0 (identity) or 1 (sigmoid)");
+  if (!d_w || !d_b) return set_error(SNF_E_INVALID, "dense layer: null weights or bias");
+  if (m > 0 && (!d_x || !d_y)) return set_error(SNF_E_INVALID, "dense layer: null buffer");
+  if (m > (int64_t(1) << 40) / std::max(k, n)) return set_error(SNF_E_INVALID, "dense layer: matrix too large");
+  if (m == 0) return SNF_OK;
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  int rc = gmm_begin(device_id, 16, stream, &t, &s);
+  if (rc) return rc;
+  rc = launch_bn_dense(d_x, m, k, d_w, d_b, n, act, d_y, nullptr, 0, 0, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "dense layer kernel failed");
+  return rc;
+}
+
+int snf_bottleneck_vad(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                       uint8_t* d_mask, int32_t* d_voiced, void* stream) {
+  int rc = bn_check_offsets(h_sample_offsets, n_utts, "sample");
+  if (rc) return rc;
+  if (n_utts == 0) return SNF_OK;
+  if (!d_voiced) return set_error(SNF_E_INVALID, "bottleneck: null voiced-count buffer");
+  std::vector<int64_t> foff;
+  bn_frame_offsets(h_sample_offsets, n_utts, &foff);
+  const int64_t total = foff[n_utts];
+  if (total > 0 && (!d_wave || !d_mask)) return set_error(SNF_E_INVALID, "bottleneck: null buffer");
+  const size_t b_off = align256(sizeof(int64_t) * (n_utts + 1));
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, 2 * b_off + sizeof(double) * std::max<int64_t>(total, 1), stream, &t, &s);
+  if (rc) return rc;
+  char* base = t->buf.as<char>();
+  int64_t* d_soff = reinterpret_cast<int64_t*>(base);
+  int64_t* d_foff = reinterpret_cast<int64_t*>(base + b_off);
+  SNF_HIP_CHECK(hipMemcpyAsync(d_soff, h_sample_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_foff, foff.data(), sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  rc = launch_bn_vad(d_wave, d_soff, d_foff, n_utts, reinterpret_cast<double*>(base + 2 * b_off), d_mask, d_voiced, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "bottleneck vad kernel failed");
+  return rc;
+}
+
+int snf_bottleneck_fbank(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                         const float* d_tables, float dither, uint64_t seed, float* d_logmel, void* stream) {
+  int rc = bn_check_offsets(h_sample_offsets, n_utts, "sample");
+  if (rc) return rc;
+  if (!(dither >= 0.0f)) return set_error(SNF_E_INVALID, "bottleneck: dither must be >= 0");
+  if (n_utts == 0) return SNF_OK;
+  std::vector<int64_t> foff;
+  bn_frame_offsets(h_sample_offsets, n_utts, &foff);
+  const int64_t total = foff[n_utts];
+  if (total == 0) return SNF_OK;
+  if (!d_wave || !d_tables || !d_logmel) return set_error(SNF_E_INVALID, "bottleneck: null buffer");
+  if (reinterpret_cast<uintptr_t>(d_tables) & 7) return set_error(SNF_E_INVALID, "bottleneck: tables are not 8-byte aligned");
+  const size_t b_off = align256(sizeof(int64_t) * (n_utts + 1));
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, 2 * b_off + sizeof(uint32_t) * n_utts, stream, &t, &s);
+  if (rc) return rc;
+  char* base = t->buf.as<char>();
+  int64_t* d_soff = reinterpret_cast<int64_t*>(base);
+  int64_t* d_foff = reinterpret_cast<int64_t*>(base + b_off);
+  SNF_HIP_CHECK(hipMemcpyAsync(d_soff, h_sample_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_foff, foff.data(), sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  rc = launch_bn_fbank(d_wave, d_soff, d_foff, n_utts, total, d_tables, dither, seed,
+                       reinterpret_cast<uint32_t*>(base + 2 * b_off), d_logmel, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "bottleneck filterbank kernel failed");
+  return rc;
+}
+
+int snf_bottleneck_nn_input(int device_id, const float* d_logmel, const uint8_t* d_mask, const int32_t* d_voiced,
+                            const int64_t* h_frame_offsets, int64_t n_utts, int32_t context, const float* d_basis,
+                            float* d_x, void* stream) {
+  int rc = bn_check_offsets(h_frame_offsets, n_utts, "frame");
+  if (rc) return rc;
+  if (context < 0 || context > bn_max_context())
+    return set_error(SNF_E_INVALID, "bottleneck: context must be in [0, " + std::to_string(bn_max_context()) + "]");
+  if (n_utts == 0) return SNF_OK;
+  std::vector<int64_t> roff(n_utts + 1, 0);
+  for (int64_t u = 0; u < n_utts; ++u) {
+    const int64_t F = h_frame_offsets[u + 1] - h_frame_offsets[u];
+    const int64_t rows = F + 2 * kBnEdge - 2 * context;
+    if (F < 1 || rows < 1)
+      return set_error(SNF_E_INVALID, "bottleneck: utterance " + std::to_string(u) + " has " + std::to_string(F) +
+                                          " frames, too few for one row at context " + std::to_string(context));
+    roff[u + 1] = roff[u] + rows;
+  }
+  if (!d_logmel || !d_mask || !d_voiced || !d_basis || !d_x) return set_error(SNF_E_INVALID, "bottleneck: null buffer");
+  const size_t b_off = align256(sizeof(int64_t) * (n_utts + 1));
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, 2 * b_off + sizeof(float) * kBnMel * n_utts, stream, &t, &s);
+  if (rc) return rc;
+  char* base = t->buf.as<char>();
+  int64_t* d_foff = reinterpret_cast<int64_t*>(base);
+  int64_t* d_roff = reinterpret_cast<int64_t*>(base + b_off);
+  SNF_HIP_CHECK(hipMemcpyAsync(d_foff, h_frame_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_roff, roff.data(), sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  rc = launch_bn_nn_input(d_logmel, d_mask, d_voiced, d_foff, d_roff, n_utts, roff[n_utts], context, d_basis,
+                          reinterpret_cast<float*>(base + 2 * b_off), d_x, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "bottleneck input kernels failed");
+  return rc;
+}
+
+int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
+                           const int32_t* h_widths, const float* const* h_params, float* d_bn, float* d_out,
+                           void* stream) {
+  int rc = bn_check_offsets(h_row_offsets, n_utts, "row");
+  if (rc) return rc;
+  if (!h_widths || !h_params) return set_error(SNF_E_INVALID, "bottleneck: null layer description");
+  for (int i = 0; i < 4; ++i)
+    if (h_widths[i] < 1 || h_widths[i] > (1 << 20))
+      return set_error(SNF_E_INVALID, "bottleneck: layer width " + std::to_string(i) + " out of range");
+  for (int i = 0; i < 12; ++i)
+    if (!h_params[i]) return set_error(SNF_E_INVALID, "bottleneck: null parameter buffer " + std::to_string(i));
+  if (n_utts == 0) return SNF_OK;
+  const int span = kBnStackStep * (kBnStack - 1);   // 20 rows of the first stage under one stacked row
+  std::vector<int64_t> ooff(n_utts + 1, 0);
+  for (int64_t u = 0; u < n_utts; ++u) {
+    const int64_t rows = h_row_offsets[u + 1] - h_row_offsets[u];
+    if (rows <= span)
+      return set_error(SNF_E_INVALID, "bottleneck: utterance " + std::to_string(u) + " has " + std::to_string(rows) +
+                                          " first-stage rows, the stack needs more than " + std::to_string(span));
+    ooff[u + 1] = ooff[u] + rows - span;
+  }
+  const int64_t R0 = h_row_offsets[n_utts], R1 = ooff[n_utts];
+  if (!d_x || !d_bn || !d_out) return set_error(SNF_E_INVALID, "bottleneck: null buffer");
+  const int wmax = std::max(std::max(h_widths[0], h_widths[1]), std::max(h_widths[2], h_widths[3]));
+  // hidden activations live in scratch, one block of rows at a time (rows are independent of each other)
+  int64_t chunk = std::max<int64_t>(1024, (int64_t(512) << 20) / (4 * int64_t(wmax))) & ~int64_t(127);
+  chunk = std::min(chunk, (R0 + 127) & ~int64_t(127));
+  const size_t b_off = align256(sizeof(int64_t) * (n_utts + 1));
+  const size_t b_map = align256(sizeof(int64_t) * R1);
+  const size_t b_hid = align256(sizeof(float) * chunk * wmax);
+  ThreadScratch* t = nullptr;
+  hipStream_t s = nullptr;
+  rc = gmm_begin(device_id, 2 * b_off + b_map + 2 * b_hid, stream, &t, &s);
+  if (rc) return rc;
+  char* base = t->buf.as<char>();
+  int64_t* d_roff = reinterpret_cast<int64_t*>(base);
+  int64_t* d_ooff = reinterpret_cast<int64_t*>(base + b_off);
+  int64_t* d_map = reinterpret_cast<int64_t*>(base + 2 * b_off);
+  float* h1 = reinterpret_cast<float*>(base + 2 * b_off + b_map);
+  float* h2 = reinterpret_cast<float*>(base + 2 * b_off + b_map + b_hid);
+  SNF_HIP_CHECK(hipMemcpyAsync(d_roff, h_row_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, s));
+  const float* const* P = h_params;
+  for (int64_t a = 0; a < R0 && !rc; a += chunk) {
+    const int64_t m = std::min(chunk, R0 - a);
+    rc = launch_bn_dense(d_x + a * kBnIn, m, kBnIn, P[0], P[1], h_widths[0], 1, h1, nullptr, 0, 0, s);
+    if (!rc) rc = launch_bn_dense(h1, m, h_widths[0], P[2], P[3], h_widths[1], 1, h2, nullptr, 0, 0, s);
+    if (!rc) rc = launch_bn_dense(h2, m, h_widths[1], P[4], P[5], kBnOut, 0, d_bn + a * kBnOut, nullptr, 0, 0, s);
+  }
+  if (!rc) rc = launch_bn_row_map(d_roff, d_ooff, n_utts, R1, d_map, s);
+  for (int64_t a = 0; a < R1 && !rc; a += chunk) {
+    const int64_t m = std::min(chunk, R1 - a);
+    rc = launch_bn_dense(d_bn, m, kBnStack * kBnOut, P[6], P[7], h_widths[2], 1, h1, d_map + a, kBnOut, kBnStackStep, s);
+    if (!rc) rc = launch_bn_dense(h1, m, h_widths[2], P[8], P[9], h_widths[3], 1, h2, nullptr, 0, 0, s);
+    if (!rc) rc = launch_bn_dense(h2, m, h_widths[3], P[10], P[11], kBnOut, 0, d_out + a * kBnOut, nullptr, 0, 0, s);
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = set_error(SNF_E_HIP, "bottleneck network kernels failed");
+  return rc;
+}
+
 int snf_malloc(void** dptr, uint64_t bytes) {
   SNF_HIP_CHECK(hipMalloc(dptr, bytes));
   return SNF_OK;

@@ -381,6 +381,23 @@ int launch_lvtln_select(const double* stats, int64_t S, int D, const double* A, 
 int launch_affine_apply_segments(const float* x, int64_t F, int D, const int64_t* off, int64_t S, const float* W,
                                  float* y, hipStream_t stream);
 
+// bottleneck extractor kernels (kernels_bottleneck.hip): see that file's header for the design
+int bn_table_floats();   // floats of the front end's table blob: window[200] | twiddles[256 x 2] | mel[129 x 24]
+int bn_max_context();
+// y = act(A w + b); `a_row` non-null: A[r][k] = x[(a_row[r] + gs (k / gw)) * gw + k % gw]
+int launch_bn_dense(const float* x, int64_t M, int K, const float* w, const float* b, int N, int act, float* y,
+                    const int64_t* a_row, int gw, int gs, hipStream_t stream);
+int launch_bn_row_map(const int64_t* in_off, const int64_t* out_off, int64_t n_utts, int64_t rows, int64_t* a_row,
+                      hipStream_t stream);
+int launch_bn_fbank(const int16_t* wave, const int64_t* soff, const int64_t* foff, int64_t n_utts,
+                    int64_t total_frames, const float* tables, float dither, uint64_t seed, uint32_t* utt_noise,
+                    float* out, hipStream_t stream);
+int launch_bn_vad(const int16_t* wave, const int64_t* soff, const int64_t* foff, int64_t n_utts, double* energy,
+                  uint8_t* mask, int32_t* voiced, hipStream_t stream);
+int launch_bn_nn_input(const float* logmel, const uint8_t* mask, const int32_t* voiced, const int64_t* foff,
+                       const int64_t* roff, int64_t n_utts, int64_t total_rows, int context, const float* hd,
+                       float* mean, float* x, hipStream_t stream);
+
 }  // namespace snf
 
 #endif  // SNF_INTERNAL_H_

@@ -18,7 +18,8 @@ be given instead (``warps=...``), not both.  ``get_default_config(with_vtln=...)
 here; build it as ``config['vtln'] = VtlnProcessor().get_params()``.  The sharded entry points
 (:mod:`shennong_amd.distributed`) take precomputed warps only.
 
-Not provided by this pipeline: CREPE pitch, bottleneck features.
+Not provided by this pipeline: CREPE pitch; bottleneck features (the processor exists -
+:class:`shennong_amd.processor.bottleneck.BottleneckProcessor` - but is not a pipeline entry yet).
 """
 
 import os

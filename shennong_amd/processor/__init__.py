@@ -16,6 +16,7 @@ _HOME = {
     'KaldiPitchPostProcessor': 'pitch_kaldi',
     'DiagUbmProcessor': 'ubm',
     'VtlnProcessor': 'vtln',
+    'BottleneckProcessor': 'bottleneck',
 }
 __all__ = sorted(_HOME)
 

@@ -1,0 +1,116 @@
+#!/usr/bin/env python
+"""Times the bottleneck extractor on one MI355X: per-stage device times (events around each C ABI call on
+device-resident audio), the whole ``process_all`` host to host, the achieved FP32 TFLOP/s of the two square
+layers (``snf_dense_layer`` alone, best of `--repeat`) and of the whole forward pass against the 157.3 TF
+FP32 matrix peak, and the ratio to the float64 numpy statement (tests/bottleneck_f64.py) on the host's CPUs.
+
+    python tools/time_bottleneck.py --utts 1000 --hidden 500 1500 [--seconds 3] [--out FILE]
+
+Prints one JSON line per configuration.  Synthetic weights (tests/bottleneck_f64.py make_weights)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import bottleneck_f64 as f64  # noqa: E402
+
+PEAK_TF = 157.3
+
+
+def corpus(n, seconds, seed=0):
+    rng = np.random.RandomState(seed)
+    length = int(8000 * seconds)
+    t = np.arange(length) / 8000.0
+    base = [np.clip(np.round((np.sin(2 * np.pi * (1.5 + 0.2 * k) * t + k) > -0.3)
+                             * (5000 * np.sin(2 * np.pi * (180 + 20 * k) * t) + 700 * rng.randn(length))
+                             + 15 * rng.randn(length)), -32768, 32767).astype(np.int16) for k in range(16)]
+    return [base[i % 16] for i in range(n)]
+
+
+def timed(fn, repeat):
+    best = float('inf')
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        fn()
+        best = min(best, time.perf_counter() - t0)
+    return best
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--utts', type=int, nargs='+', default=[1000])
+    ap.add_argument('--hidden', type=int, nargs='+', default=[500, 1500])
+    ap.add_argument('--seconds', type=float, default=3.0)
+    ap.add_argument('--repeat', type=int, default=3)
+    ap.add_argument('--cpu-utts', type=int, default=8)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    from shennong_amd import Audio, Utterances, _backend
+    from shennong_amd.processor import bottleneck
+    lines = []
+    for hidden in args.hidden:
+        weights = f64.make_weights(1, hidden, 5)
+        tmp = tempfile.mkdtemp(prefix='bottleneck_weights_')   # (looked up again by every call: kept)
+        os.environ[bottleneck.ENV_DIR] = tmp
+        np.savez(os.path.join(tmp, bottleneck._FILES['BabelMulti'] + '.npz'), **weights)
+        proc = bottleneck.BottleneckProcessor(dither=0.0)
+        dnet = proc._device_network(_backend.get_device())
+        # the square layer alone: 65 536 rows (calls wait for their stream: host to host = device time + launch)
+        rng = np.random.RandomState(2)
+        m = 65536
+        x = _backend.DeviceBuffer(4 * m * hidden)
+        y = _backend.DeviceBuffer(4 * m * hidden)
+        x.upload(rng.uniform(0, 1, (m, hidden)).astype(np.float32))
+        L = _backend.lib()
+
+        def square():
+            _backend.check(L.snf_dense_layer(_backend.get_device(), C.c_void_p(x.ptr), m, hidden,
+                                             C.c_void_p(dnet.buffers[2].ptr), C.c_void_p(dnet.buffers[3].ptr),
+                                             hidden, 1, C.c_void_p(y.ptr), None))
+        square()
+        sq = timed(square, args.repeat)
+        for n in args.utts:
+            waves = corpus(n, args.seconds)
+            batch = bottleneck.BottleneckBatch(waves)
+            batch.vad(); batch.fbank(0.0); batch.forward(dnet)   # warm-up (scratch, tables)
+            t_vad = timed(batch.vad, args.repeat)
+            t_fb = timed(lambda: batch.fbank(0.0), args.repeat)
+            t_fw = timed(lambda: batch.forward(dnet), args.repeat)
+            r0, r1 = int(batch.roff[-1]), int(batch.ooff[-1])
+            flop = 2.0 * (r0 * (144 * hidden + hidden * hidden + hidden * 80)
+                          + r1 * (400 * hidden + hidden * hidden + hidden * 80))
+            utts = Utterances([('u%05d' % i, Audio(w, 8000, validate=False)) for i, w in enumerate(waves)])
+            proc.process_all(utts)
+            t_all = timed(lambda: proc.process_all(utts), args.repeat)
+            k = min(args.cpu_utts, n)
+            t0 = time.perf_counter()
+            for w in waves[:k]:
+                f64.extract(w, weights)
+            t_cpu = (time.perf_counter() - t0) / k * n
+            lines.append({
+                'hidden': hidden, 'utts': n, 'seconds_each': args.seconds, 'device': _backend.device_name(),
+                'vad_ms': 1e3 * t_vad, 'fbank_ms': 1e3 * t_fb,
+                'nn_input_forward_download_ms': 1e3 * t_fw, 'process_all_ms': 1e3 * t_all,
+                'forward_flop': flop, 'forward_tflops_incl_input_and_download': flop / t_fw / 1e12,
+                'square_layer_rows': m, 'square_layer_ms': 1e3 * sq,
+                'square_layer_tflops': 2.0 * m * hidden * hidden / sq / 1e12,
+                'square_layer_fraction_of_peak': 2.0 * m * hidden * hidden / sq / 1e12 / PEAK_TF,
+                'numpy_f64_ms_extrapolated_from': k, 'numpy_f64_ms': 1e3 * t_cpu,
+                'speedup_vs_numpy_f64': t_cpu / t_all})
+            print(json.dumps(lines[-1]), flush=True)
+    if args.out:
+        with open(args.out, 'w') as fh:
+            for line in lines:
+                fh.write(json.dumps(line) + '\n')
+
+
+if __name__ == '__main__':
+    main()
