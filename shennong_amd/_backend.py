@@ -1209,7 +1209,7 @@ class _DevicePool:
             self._bytes = 0
         # (binds the thread to every device that has parked blocks: callers re-bind afterwards -
         # DeviceBuffer.__init__ below; the library's out-of-memory hook, which also runs this in the middle of
-        # a plan call, saves and restores the thread's device around it: csrc/capi.hip malloc_with_hook)
+        # a plan call, saves and restores the thread's device around it: csrc/capi_runtime.hip malloc_with_hook)
         for device, block in blocks:
             bind_device(device)
             lib().snf_free(C.c_void_p(block[1]))

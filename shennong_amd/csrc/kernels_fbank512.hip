@@ -1589,9 +1589,14 @@ int fast512_build(const MelParams& mp, const std::vector<float>& window, const M
 }
 
 int launch_fbank512(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
-                    double* energy_out, hipStream_t stream) {
+                    double* energy_out, hipStream_t stream, const char** launched) {
+  const char* unnamed;
+  if (!launched) launched = &unnamed;
+  *launched = nullptr;
   if (b.total_frames <= 0) return SNF_OK;
-  if (fbank512b_eligible(p, b)) return launch_fbank512b(p, b, out, out_cols, energy_out, stream);
+  const bool b_form = fbank512b_eligible(p, b);
+  *launched = b_form ? "fbank512b_kernel" : p.dual ? "fbank256x2_kernel" : "fbank512_kernel";
+  if (b_form) return launch_fbank512b(p, b, out, out_cols, energy_out, stream);
   Fast512Params q = p;
   q.out_cols = out_cols;
   const bool per_utt = b.blk_utt != nullptr;

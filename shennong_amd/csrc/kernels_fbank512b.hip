@@ -475,17 +475,21 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
 // host side
 // ---------------------------------------------------------------------------------------------------
 // Flat batches (no per-utterance warps, no fused deltas), snip_edges, vector-pipe DCT; dither when the caller
-// made the frames' key table (capi.hip).
+// made the frames' key table.  fbank512b_shape_ok is everything but the key table: the host layer
+// (capi_mel.hip: route_mel_batch) makes the table for exactly the batches that pass it.
 // SNF_FBANK512_OLD=1 keeps every batch on fbank512_kernel (A/B runs: tools/ab_fbank512.cpp, bench.py).
-bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b) {
+bool fbank512b_shape_ok(const Fast512Params& p, bool per_utt) {
   if (const char* knob = getenv("SNF_FBANK512_OLD"))
     if (knob[0] == '1') return false;
-  if (p.dual || p.fused_delta || b.blk_utt != nullptr) return false;
+  if (p.dual || p.fused_delta || per_utt) return false;
   if (!p.snip_edges || p.dct_mfma) return false;
-  if (p.dither != 0.0f && b.frame_noise == nullptr) return false;  // (no key table: fbank512_kernel draws its own)
   // (the spectrogram's four 16-byte row stores per lane measured 7 % slower here than on fbank512_kernel)
   if (p.kind != SNF_KIND_FBANK && p.kind != SNF_KIND_MFCC && p.kind != SNF_KIND_PLP) return false;
   return static_cast<size_t>((p.table_floats * 4 + 255) & ~255) + kWaves * 4 * kTileBytes <= 160 * 1024;
+}
+bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b) {
+  if (p.dither != 0.0f && b.frame_noise == nullptr) return false;  // (no key table: fbank512_kernel draws its own)
+  return fbank512b_shape_ok(p, b.blk_utt != nullptr);
 }
 
 namespace {

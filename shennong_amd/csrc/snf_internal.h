@@ -50,7 +50,7 @@ struct MelBanksHost {
 int make_mel_banks(const snf_mel_options& mo, const snf_frame_options& fo, float vtln_warp,
                    MelBanksHost* out);
 // structurally valid banks with zero weights: what a PLP plan holds in place of unwarped banks that the
-// options do not allow, until an utterance asks for them (capi.hip: snf_plan::base_banks_error)
+// options do not allow, until an utterance asks for them (plan.h: snf_plan::base_banks_error)
 void make_placeholder_banks(const snf_mel_options& mo, const snf_frame_options& fo, MelBanksHost* out);
 void make_dct_matrix(int num_rows, int num_cols, std::vector<float>* m);  // first rows of NxN DCT
 void make_lifter(float q, int n, std::vector<float>* c);
@@ -248,8 +248,10 @@ int launch_build_frame_start(const int64_t* d_frame_offsets, const int64_t* d_sa
                              int64_t n_utts, int64_t total_frames, int64_t total_samples, int win_shift,
                              int win_len, int snip_edges, int64_t* d_frame_start, int32_t* d_frame_edge,
                              int32_t* d_frame_utt, hipStream_t stream);
+// `launched`: receives the name of the kernel the call went to (fbank512b_kernel, fbank256x2_kernel or
+// fbank512_kernel; nullptr: none)
 int launch_fbank512(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
-                    double* energy_out, hipStream_t stream);
+                    double* energy_out, hipStream_t stream, const char** launched = nullptr);
 // per-call table of the frames' noise keys (wave_noise_id: the dither of fbank512b_kernel; the keys hold
 // the first two samples of the utterance, so they are rebuilt with every batch)
 int launch_build_frame_noise(const BatchArgs& b, uint64_t* d_keys, hipStream_t stream);
@@ -257,6 +259,8 @@ int launch_build_frame_noise(const BatchArgs& b, uint64_t* d_keys, hipStream_t s
 int launch_build_utt_noise(const BatchArgs& b, uint32_t* d_words, hipStream_t stream);
 // the occupancy-first form of the same kernel (kernels_fbank512b.hip): flat, snip_edges batches
 bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b);
+// ... everything of it that does not depend on the frames' noise key table: whoever makes that table asks this
+bool fbank512b_shape_ok(const Fast512Params& p, bool per_utt);
 int launch_fbank512b(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
                      double* energy_out, hipStream_t stream);
 

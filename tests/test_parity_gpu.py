@@ -826,7 +826,7 @@ def test_features_do_not_depend_on_the_warps_of_the_batch(gpu, cls, sample_rate)
                                               (FilterbankProcessor, 32000), (PlpProcessor, 22050)])
 def test_every_route_in_one_batch(gpu, cls, sample_rate):
     """snip_edges = False, VTLN warps and utterances shorter than a window together: warped / unwarped /
-    sub-window utterances each take their own kernel inside one call (capi.hip: split_dual, run_short),
+    sub-window utterances each take their own kernel inside one call (capi_mel.hip: dual256_split, run_short),
     also when one of the groups is empty; every utterance agrees with the oracle and with itself alone"""
     win = int(round(0.025 * sample_rate))
     n = int(0.3 * sample_rate)
@@ -1578,7 +1578,7 @@ def test_adversarial_waveforms(gpu):
     dict(num_bins=128, low_freq=700, vtln_low=800), dict(num_bins=112, low_freq=400, vtln_low=500, frame_length=0.03)])
 def test_wide_filterbanks(gpu, synth_waves, opts):
     """filterbanks of 65 ... 128 bins (fbank-80 at 16 kHz) run the 64-bin kernel twice, over the two halves of the
-    bank (capi.hip: snf_plan::wide) - until round 6 they fell to the generic kernel; the energy column goes with
+    bank (plan.h: snf_plan::wide) - until round 6 they fell to the generic kernel; the energy column goes with
     the half it is adjacent to; VTLN batches of such banks stay on the generic kernel; alone == in a batch"""
     waves = list(synth_waves)
     proc = FilterbankProcessor(dither=0, **opts)
