@@ -470,6 +470,44 @@ int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row
                            const int32_t* h_widths, const float* const* h_params, float* d_bn, float* d_out,
                            void* stream);
 
+/* ---- CREPE pitch (reference processor/pitch_crepe.py, CrepePitchProcessor) -------------------------
+ * The CREPE network on 16 kHz int16 audio: frames of 1024 samples every `hop`, a signal of n samples gives
+ * 1 + (n + (center ? 1024 : 0) - 1024) / hop of them (it must hold at least one).  Six blocks of convolution,
+ * ReLU, batch normalisation (inference form, given as scale and shift per channel) and max-pool 2, then a
+ * dense layer of 360 sigmoids; float32 on the FP32 matrix cores, every element summed in one fixed order
+ * (fused multiply-add chains over 256 consecutive k ascending, their results added in ascending order), so an
+ * utterance gives the same bits alone and in any batch.  Offsets tables are HOST int64
+ * (non-decreasing, first 0), every other buffer is on the device.  `stream` NULL: the calling thread's own
+ * stream; every call waits for its stream before returning.  Invalid arguments return SNF_E_INVALID before any
+ * device work.
+ */
+/* One convolution block on channels-last activations d_x[frames x in_len x c_in]: `width` taps at `stride`
+ * with `pad_left` zeros before position 0 (and zeros after the last), positions = output positions before the
+ * pool (even when pooled): ceil(in_len / stride) for "same" padding, fewer are allowed, more are invalid; d_w[width * c_in x c_out] row-major (the Keras kernel), flags: 1 = ReLU then
+ * * d_scale + d_shift, 2 = maximum over position pairs, 4 = logistic sigmoid.  d_y[frames x positions (/ 2)
+ * x c_out]. */
+int snf_crepe_conv(int device_id, const float* d_x, int64_t frames, int32_t in_len, int32_t c_in, int32_t width,
+                   int32_t stride, int32_t pad_left, int32_t positions, const float* d_w, const float* d_b,
+                   const float* d_scale, const float* d_shift, int32_t c_out, int32_t flags, float* d_y,
+                   void* stream);
+/* Ingest (zero padding of 512 samples on either side when `center`, per-frame mean and deviation from
+ * float64 sums in a fixed order, deviation floored at 1e-8) and the whole network, one block of frames at a
+ * time: h_filters[6] the channels of the six blocks, h_params[26] HOST array of DEVICE pointers, per block
+ * kernel [K x C], bias, scale, shift, then the classifier's kernel [4 C6 x 360] and bias.
+ * d_activation[total_frames x 360]. */
+int snf_crepe_forward(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                      int32_t hop, int32_t center, const int32_t* h_filters, const float* const* h_params,
+                      float* d_activation, void* stream);
+/* Decoders over d_activation[total_frames x 360]: per frame the maximum (the confidence) and its first
+ * index; `viterbi` != 0: the most likely path of the reference's 360-state model over those indices (float64
+ * log domain, first index on ties); the weighted average of cents over bins [c - 4, c + 5) around the chosen
+ * bin c, then 10 * 2^(cents / 1200) (0 where that is NaN).  d_tables float64, built by the host: log
+ * transition band [360 x 23] (entry (j, d) = log A[j - 11 + d][j]) | log start | log emission of the state's own
+ * symbol | of another symbol | cents of the 360 bins.  d_out[total_frames x 2] float64 (confidence, Hertz),
+ * d_bins[2 x total_frames] int32 (first argmax, chosen bin). */
+int snf_crepe_decode(int device_id, const float* d_activation, const int64_t* h_frame_offsets, int64_t n_utts,
+                     int32_t viterbi, const double* d_tables, double* d_out, int32_t* d_bins, void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

@@ -43,7 +43,8 @@ EXPORTS = [
     'snf_gmm_loglikes', 'snf_gmm_accumulate', 'snf_gmm_gselect', 'snf_gmm_gselect_preselect',
     'snf_gmm_selection_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
     'snf_affine_apply_segments', 'snf_vtln_gram_rows', 'snf_dense_layer', 'snf_bottleneck_vad',
-    'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward']
+    'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward', 'snf_crepe_conv',
+    'snf_crepe_forward', 'snf_crepe_decode']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -171,6 +172,9 @@ def lib():
         L.snf_bottleneck_fbank.argtypes = [i32, vp, pi64, i64, vp, f32, C.c_uint64, vp, vp]
         L.snf_bottleneck_nn_input.argtypes = [i32, vp, vp, vp, pi64, i64, i32, vp, vp, vp]
         L.snf_bottleneck_forward.argtypes = [i32, vp, pi64, i64, pi32, C.POINTER(vp), vp, vp, vp]
+        L.snf_crepe_conv.argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp]
+        L.snf_crepe_forward.argtypes = [i32, vp, pi64, i64, i32, i32, pi32, C.POINTER(vp), vp, vp]
+        L.snf_crepe_decode.argtypes = [i32, vp, pi64, i64, i32, vp, vp, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)

@@ -1,0 +1,136 @@
+// C ABI of libshennong_hip.so (include/shennong_amd.h): the plan-less CREPE entry points - one convolution
+// block, the whole network from the resident audio, the decoders.  Each runs on the calling thread's scratch
+// and stream (plan.h: Planless).
+#include <algorithm>
+
+#include "plan.h"
+
+using namespace snf;
+
+extern "C" {
+
+namespace {
+constexpr int kFrame = 1024, kBins = 360, kBlocks = 6, kMaxFilters = 1 << 14;
+
+int crepe_check_offsets(const int64_t* h_off, int64_t n, const char* what) {
+  if (n < 0) return set_error(SNF_E_INVALID, "crepe: number of utterances < 0");
+  if (!h_off) return set_error(SNF_E_INVALID, std::string("crepe: null ") + what + " offsets table");
+  if (h_off[0] != 0) return set_error(SNF_E_INVALID, std::string("crepe: ") + what + " offsets must start at 0");
+  for (int64_t u = 0; u < n; ++u)
+    if (h_off[u + 1] < h_off[u])
+      return set_error(SNF_E_INVALID, std::string("crepe: ") + what + " offsets must not decrease");
+  if (h_off[n] > (int64_t(1) << 40)) return set_error(SNF_E_INVALID, "crepe: batch too large");
+  return SNF_OK;
+}
+}  // namespace
+
+int snf_crepe_conv(int device_id, const float* d_x, int64_t frames, int32_t in_len, int32_t c_in, int32_t width,
+                   int32_t stride, int32_t pad_left, int32_t positions, const float* d_w, const float* d_b,
+                   const float* d_scale, const float* d_shift, int32_t c_out, int32_t flags, float* d_y,
+                   void* stream) {
+  if (frames < 0) return set_error(SNF_E_INVALID, "crepe conv: number of frames < 0");
+  if (in_len < 1 || c_in < 1 || width < 1 || stride < 1 || pad_left < 0 || positions < 1 || c_out < 1)
+    return set_error(SNF_E_INVALID, "crepe conv: sizes must be at least 1 (pad_left 0)");
+  if (c_in > kMaxFilters || c_out > kMaxFilters || in_len > (1 << 16) || width > (1 << 16) || stride > (1 << 16) ||
+      pad_left > (1 << 16) || positions > (1 << 16) || int64_t(width) * c_in > (1 << 24) ||
+      int64_t(in_len) * c_in > (1 << 24) || int64_t(positions) * stride * c_in > (int64_t(1) << 30))
+    return set_error(SNF_E_INVALID, "crepe conv: sizes out of range");
+  if (positions > (in_len + stride - 1) / stride)   // more would be rows of padding alone
+    return set_error(SNF_E_INVALID, "crepe conv: more positions than ceil(in_len / stride)");
+  if (flags & ~(kConvNorm | kConvPool | kConvSigmoid)) return set_error(SNF_E_INVALID, "crepe conv: unknown flag");
+  if ((flags & kConvPool) && positions % 2) return set_error(SNF_E_INVALID, "crepe conv: the pool needs an even number of positions");
+  if (!d_w || !d_b) return set_error(SNF_E_INVALID, "crepe conv: null kernel or bias");
+  if ((flags & kConvNorm) && (!d_scale || !d_shift)) return set_error(SNF_E_INVALID, "crepe conv: null scale or shift");
+  if (frames > 0 && (!d_x || !d_y)) return set_error(SNF_E_INVALID, "crepe conv: null buffer");
+  if (frames > (int64_t(1) << 40) / (int64_t(std::max(in_len, positions)) * std::max(c_in, c_out)))
+    return set_error(SNF_E_INVALID, "crepe conv: block too large");
+  if (frames == 0) return SNF_OK;
+  Planless lay;
+  int rc = lay.begin(device_id, stream);
+  if (rc) return rc;
+  rc = launch_crepe_conv(d_x, frames, positions, stride * c_in, pad_left * c_in, in_len * c_in, width * c_in, d_w, d_b,
+                         d_scale, d_shift, c_out, flags, d_y, lay.s);
+  return lay.finish(rc, "crepe convolution kernel failed");
+}
+
+int snf_crepe_forward(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                      int32_t hop, int32_t center, const int32_t* h_filters, const float* const* h_params,
+                      float* d_activation, void* stream) {
+  int rc = crepe_check_offsets(h_sample_offsets, n_utts, "sample");
+  if (rc) return rc;
+  if (hop < 1 || hop > (1 << 20)) return set_error(SNF_E_INVALID, "crepe: hop must be in [1, 2^20] samples");
+  if (!h_filters || !h_params) return set_error(SNF_E_INVALID, "crepe: null network description");
+  for (int l = 0; l < kBlocks; ++l)
+    if (h_filters[l] < 1 || h_filters[l] > kMaxFilters)
+      return set_error(SNF_E_INVALID, "crepe: filters of block " + std::to_string(l + 1) + " out of range");
+  for (int i = 0; i < 4 * kBlocks + 2; ++i)
+    if (!h_params[i]) return set_error(SNF_E_INVALID, "crepe: null parameter buffer " + std::to_string(i));
+  if (n_utts == 0) return SNF_OK;
+  std::vector<int64_t> foff(n_utts + 1, 0);
+  for (int64_t u = 0; u < n_utts; ++u) {
+    const int64_t padded = h_sample_offsets[u + 1] - h_sample_offsets[u] + (center ? kFrame : 0);
+    if (padded < kFrame)
+      return set_error(SNF_E_INVALID, "crepe: utterance " + std::to_string(u) + " is shorter than one frame of 1024 samples");
+    foff[u + 1] = foff[u] + 1 + (padded - kFrame) / hop;
+  }
+  const int64_t total = foff[n_utts];
+  if (!d_wave || !d_activation) return set_error(SNF_E_INVALID, "crepe: null buffer");
+  // activations live in scratch, one block of frames at a time (frames are independent of each other):
+  // `even` holds the frames and the outputs of blocks 2, 4, 6, `odd` those of blocks 1, 3, 5
+  const int32_t* C = h_filters;
+  int64_t even = kFrame, odd = 0;
+  for (int l = 0, T = 128; l < kBlocks; ++l, T /= 2) {
+    int64_t& side = (l % 2) ? even : odd;
+    side = std::max(side, int64_t(T) * C[l]);
+  }
+  int64_t chunk = std::max<int64_t>(64, (int64_t(512) << 20) / (4 * (even + odd)));
+  chunk = std::min(chunk, total);
+  Planless lay;
+  auto d_soff = lay.take<int64_t>(n_utts + 1);
+  auto d_foff = lay.take<int64_t>(n_utts + 1);
+  auto buf_even = lay.take<float>(chunk * even);
+  auto buf_odd = lay.take<float>(chunk * odd);
+  if ((rc = lay.begin(device_id, stream))) return rc;
+  SNF_HIP_CHECK(hipMemcpyAsync(d_soff, h_sample_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, lay.s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_foff, foff.data(), sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, lay.s));
+  const float* const* P = h_params;
+  for (int64_t a = 0; a < total && !rc; a += chunk) {
+    const int64_t m = std::min(chunk, total - a);
+    float* src = buf_even;
+    float* dst = buf_odd;
+    rc = launch_crepe_frames(d_wave, d_soff, d_foff, n_utts, a, m, hop, center ? 1 : 0, src, lay.s);
+    // block 1: 512 taps at stride 4 over the 1024 samples, 254 zeros before; blocks 2..6: 64 taps, 31 before
+    if (!rc) rc = launch_crepe_conv(src, m, 256, 4, 254, kFrame, 512, P[0], P[1], P[2], P[3], C[0],
+                                    kConvNorm | kConvPool, dst, lay.s);
+    for (int l = 1, T = 128; l < kBlocks && !rc; ++l, T /= 2) {
+      std::swap(src, dst);
+      rc = launch_crepe_conv(src, m, T, C[l - 1], 31 * C[l - 1], T * C[l - 1], 64 * C[l - 1], P[4 * l], P[4 * l + 1],
+                             P[4 * l + 2], P[4 * l + 3], C[l], kConvNorm | kConvPool, dst, lay.s);
+    }
+    // classifier: the 4 positions x C6 channels of a frame are its row, time-major with channels innermost
+    if (!rc) rc = launch_crepe_conv(dst, m, 1, 4 * C[5], 0, 4 * C[5], 4 * C[5], P[24], P[25], nullptr, nullptr, kBins,
+                                    kConvSigmoid, d_activation + a * kBins, lay.s);
+  }
+  return lay.finish(rc, "crepe network kernels failed");
+}
+
+int snf_crepe_decode(int device_id, const float* d_activation, const int64_t* h_frame_offsets, int64_t n_utts,
+                     int32_t viterbi, const double* d_tables, double* d_out, int32_t* d_bins, void* stream) {
+  int rc = crepe_check_offsets(h_frame_offsets, n_utts, "frame");
+  if (rc) return rc;
+  if (n_utts == 0 || h_frame_offsets[n_utts] == 0) return SNF_OK;
+  const int64_t total = h_frame_offsets[n_utts];
+  if (!d_activation || !d_tables || !d_out || !d_bins) return set_error(SNF_E_INVALID, "crepe: null buffer");
+  if (reinterpret_cast<uintptr_t>(d_tables) & 7) return set_error(SNF_E_INVALID, "crepe: tables are not 8-byte aligned");
+  Planless lay;
+  auto d_foff = lay.take<int64_t>(n_utts + 1);
+  auto conf = lay.take<float>(total);
+  auto psi = lay.take<uint16_t>(viterbi ? total * kBins : 0);
+  if ((rc = lay.begin(device_id, stream))) return rc;
+  SNF_HIP_CHECK(hipMemcpyAsync(d_foff, h_frame_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, lay.s));
+  rc = launch_crepe_decode(d_activation, d_foff, n_utts, total, viterbi ? 1 : 0, d_tables, conf, psi, d_bins, d_out,
+                           lay.s);
+  return lay.finish(rc, "crepe decoder kernels failed");
+}
+
+}  // extern "C"

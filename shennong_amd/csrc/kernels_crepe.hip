@@ -1,0 +1,416 @@
+// CREPE pitch tracker (Kim et al., ICASSP 2018; reference processor/pitch_crepe.py): frame ingest, the six
+// convolution blocks and the classifier on the FP32 matrix cores, and the decoders.
+//
+// Convolution (crepe_conv_kernel): an implicit GEMM Y = epilogue(A W), the tiling of bn_dense_kernel
+// (kernels_bottleneck.hip: block 128 x 128 x 32, 4 waves of 2 x 2 tiles of v_mfma_f32_32x32x2_f32, LDS strides
+// 34 / 160, register prefetch of the next k tile).
+//   * Activations are channels-last, [frame][position][channel].  Output row r = (frame f, position t) of a
+//     layer with T positions reads ONE contiguous run of K = width * C_in floats of its frame's block of L
+//     floats, from s = (t * stride - pad_left) * C_in on; what falls outside [0, L) is the zero padding.  The A
+//     loader therefore takes a base (f L), an offset (s) and a bound (L) per row, computed once per thread for
+//     its four rows; the im2col matrix is never written.  Layer 1 is the same with C_in = 1, stride 4, K = 512
+//     (offsets are not multiples of 4 floats there: scalar loads); the classifier is T = 1, s = 0, K = L.
+//   * W is the Keras kernel [width][1][C_in][C_out] read as a row-major [K x N] matrix: k = tap * C_in + channel,
+//     the order of the run above.
+//   * Epilogue per element: + bias, ReLU, * scale[c] + shift[c] (the inference form of the batch normalisation,
+//     applied AFTER the ReLU as the network does, not folded anywhere: the next layer zero-pads this output, and
+//     a negative scale does not commute with the pool), then the maximum over the position pair (2p, 2p + 1).
+//     In the accumulator layout a lane holds rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) of one column, so
+//     the pair is registers reg, reg + 1 of the same lane: the pool costs one v_max and the output is written
+//     once, already pooled.  The classifier's epilogue is + bias and the logistic sigmoid.
+//   * Summation order, fixed per element: chains of fused multiply-adds over kChain = 256 consecutive k
+//     ascending from a zero accumulator (padding adds fma(0, w, acc) = acc), the chains' results added in
+//     ascending order.  The value depends on the frame's own samples only, not on the batch or the tiling.
+//     One chain over all k (as in bn_dense_kernel) was measured first: at the full model's K = 65 536 its
+//     round-off (about sqrt(K) eps times the running sum) was 19.5 times that of float32 numpy on the host.
+//
+// Ingest (crepe_frames_kernel): one workgroup per frame, int16 samples straight from the resident audio (the
+// 512 zeros on either side of a centred signal are an index test, no padded copy exists); mean and deviation
+// from float64 sums in a fixed order (4 samples per thread ascending, then a binary tree in LDS).
+//
+// Decoders: row maximum and first argmax (one wave per frame), the 360-state Viterbi smoothing over the
+// argmax observations in float64 log domain (one workgroup per utterance, a band of +-11 states, first index
+// on ties, back pointers in scratch), the weighted average of cents around the chosen bin, cents to Hertz.
+#include <math.h>
+
+#include "snf_internal.h"
+#include "device_fft.h"
+
+namespace snf {
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kBM = 128, kBN = 128, kBK = 32;
+constexpr int kLdA = 34;    // floats per A row in LDS
+constexpr int kLdB = 160;   // floats per B k-row in LDS
+constexpr int kThreads = 256;
+constexpr int kChain = 256;   // k per multiply-add chain (a multiple of kBK)
+
+constexpr int kFrame = 1024, kHalf = 512, kBinsOut = 360, kBand = 11, kBandW = 2 * kBand + 1;
+// float64 offsets in the decoder's table blob
+constexpr int kTabTrans = 0, kTabStart = kBinsOut * kBandW, kTabSame = kTabStart + 1, kTabOther = kTabStart + 2,
+              kTabCents = kTabStart + 3;
+
+struct ConvArgs {
+  const float* x;
+  const float* w;
+  const float* b;
+  const float* scale;
+  const float* shift;
+  float* y;
+  int64_t M;       // rows: frames * T
+  int K, N;
+  int T;           // output positions per frame before the pool
+  int step;        // floats between the runs of consecutive positions: stride * C_in
+  int lead;        // floats of zero padding before position 0's run: pad_left * C_in
+  int L;           // floats of one frame's input block
+  int flags;       // kConvNorm | kConvPool | kConvSigmoid
+  int vec_a, vec_b;
+};
+
+__device__ __forceinline__ float crepe_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// 4 consecutive k of the row whose run starts `s` floats into the frame block at `base`; zeros outside
+__device__ __forceinline__ float4 load_a4(const ConvArgs& g, bool row_ok, int64_t base, int s, int k) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (!row_ok || k >= g.K) return v;
+  const int p = s + k;
+  if (g.vec_a) {   // s, k, L and K are multiples of 4: the four floats are inside together or not at all
+    if (p < 0 || p >= g.L) return v;
+    return *reinterpret_cast<const float4*>(g.x + base + p);
+  }
+  float t[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (k + j < g.K && p + j >= 0 && p + j < g.L) t[j] = g.x[base + p + j];
+  return make_float4(t[0], t[1], t[2], t[3]);
+}
+
+__device__ __forceinline__ float4 load_b4(const ConvArgs& g, int k, int n) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (k >= g.K || n >= g.N) return v;
+  const float* p = g.w + static_cast<int64_t>(k) * g.N + n;
+  if (g.vec_b) return *reinterpret_cast<const float4*>(p);
+  v.x = p[0];
+  if (n + 1 < g.N) v.y = p[1];
+  if (n + 2 < g.N) v.z = p[2];
+  if (n + 3 < g.N) v.w = p[3];
+  return v;
+}
+
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) crepe_conv_kernel(const ConvArgs g, int n_tiles_n) {
+  __shared__ __attribute__((aligned(16))) float As[kBM * kLdA];
+  __shared__ __attribute__((aligned(16))) float Bs[kBK * kLdB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
+  const int64_t m0 = static_cast<int64_t>(blockIdx.x / n_tiles_n) * kBM;
+  const int n0 = static_cast<int>(blockIdx.x % n_tiles_n) * kBN;
+  const int a_kq = tid & 7, a_m = tid >> 3;     // A: rows a_m + 32 i, columns 4 a_kq ..
+  const int b_nq = tid & 31, b_k = tid >> 5;    // B: k rows b_k + 8 i, columns 4 b_nq ..
+  int64_t a_base[4];
+  int a_s[4];
+  bool a_ok[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t r = m0 + a_m + 32 * i;
+    a_ok[i] = r < g.M;
+    const int64_t f = a_ok[i] ? r / g.T : 0;
+    const int t = a_ok[i] ? static_cast<int>(r - f * g.T) : 0;
+    a_base[i] = f * g.L;
+    a_s[i] = t * g.step - g.lead;
+  }
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+  f32x16 sum[2][2];   // the partial sums of the k blocks done so far, added in ascending order
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sum[a][b][r] = 0.0f;
+  float4 ra[4], rb[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ra[i] = load_a4(g, a_ok[i], a_base[i], a_s[i], 4 * a_kq);
+    rb[i] = load_b4(g, b_k + 8 * i, n0 + 4 * b_nq);
+  }
+  for (int k0 = 0; k0 < g.K; k0 += kBK) {
+    __syncthreads();   // the previous tile's operand reads are done
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float2* pa = reinterpret_cast<float2*>(As + (a_m + 32 * i) * kLdA + 4 * a_kq);
+      pa[0] = make_float2(ra[i].x, ra[i].y);
+      pa[1] = make_float2(ra[i].z, ra[i].w);
+      *reinterpret_cast<float4*>(Bs + (b_k + 8 * i) * kLdB + 4 * b_nq) = rb[i];
+    }
+    __syncthreads();
+    if (k0 + kBK < g.K) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ra[i] = load_a4(g, a_ok[i], a_base[i], a_s[i], k0 + kBK + 4 * a_kq);
+        rb[i] = load_b4(g, k0 + kBK + b_k + 8 * i, n0 + 4 * b_nq);
+      }
+    }
+    const int kmax = min(kBK, (g.K - k0 + 1) & ~1);
+    const float* pa = As + (wm * 64 + li) * kLdA + lh;
+    const float* pb = Bs + lh * kLdB + wn * 64 + li;
+    for (int kk = 0; kk < kmax; kk += 2) {
+      const float a0 = pa[kk], a1 = pa[32 * kLdA + kk];
+      const float b0 = pb[kk * kLdB], b1 = pb[kk * kLdB + 32];
+      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+    if ((k0 + kBK) % kChain == 0 || k0 + kBK >= g.K) {   // a chain of kChain k is complete (or K is)
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            sum[a][b][r] += acc[a][b][r];
+            acc[a][b][r] = 0.0f;
+          }
+    }
+  }
+  // epilogue: bias, ReLU and normalisation or sigmoid, the pool over the row pair, one store per output
+  const bool norm = g.flags & kConvNorm, pool = g.flags & kConvPool, sigm = g.flags & kConvSigmoid;
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn) {
+    const int c = n0 + wn * 64 + tn * 32 + li;
+    if (c >= g.N) continue;
+    const float bias = g.b[c];
+    const float sc = norm ? g.scale[c] : 1.0f, sh = norm ? g.shift[c] : 0.0f;
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const int64_t row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;   // even; r + 1 is row + 1
+        float v0 = sum[tm][tn][r] + bias, v1 = sum[tm][tn][r + 1] + bias;
+        if (norm) {
+          v0 = fmaf(fmaxf(v0, 0.0f), sc, sh);
+          v1 = fmaf(fmaxf(v1, 0.0f), sc, sh);
+        }
+        if (sigm) {
+          v0 = crepe_sigmoid(v0);
+          v1 = crepe_sigmoid(v1);
+        }
+        if (pool) {   // (M is even: the pair is inside together)
+          if (row < g.M) g.y[(row >> 1) * g.N + c] = fmaxf(v0, v1);
+        } else {
+          if (row < g.M) g.y[row * g.N + c] = v0;
+          if (row + 1 < g.M) g.y[(row + 1) * g.N + c] = v1;
+        }
+      }
+    }
+  }
+}
+
+// ---- ingest ---------------------------------------------------------------------------------------------
+// frames [first, first + count) of the batch, normalised, to out[count x 1024]
+__global__ void __launch_bounds__(kThreads) crepe_frames_kernel(const int16_t* __restrict__ wave,
+                                                               const int64_t* __restrict__ soff,
+                                                               const int64_t* __restrict__ foff, int64_t n_utts,
+                                                               int64_t first, int hop, int center,
+                                                               float* __restrict__ out) {
+  __shared__ double red[kThreads];
+  const int64_t g = first + blockIdx.x;
+  const int64_t u = find_utt(foff, n_utts, g);
+  const int64_t len = soff[u + 1] - soff[u];
+  const int64_t start = (g - foff[u]) * hop - (center ? kHalf : 0);
+  const int16_t* src = wave + soff[u];
+  float x[4];
+  double s = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int64_t i = start + 4 * threadIdx.x + j;
+    x[j] = (i >= 0 && i < len) ? static_cast<float>(src[i]) : 0.0f;
+    s += static_cast<double>(x[j]);
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  const float mean = static_cast<float>(red[0] / kFrame);
+  __syncthreads();
+  s = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    x[j] -= mean;
+    s += static_cast<double>(x[j]) * static_cast<double>(x[j]);
+  }
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  const float dev = fmaxf(static_cast<float>(sqrt(red[0] / kFrame)), 1e-8f);
+  float4 v = make_float4(x[0] / dev, x[1] / dev, x[2] / dev, x[3] / dev);
+  reinterpret_cast<float4*>(out + static_cast<int64_t>(blockIdx.x) * kFrame)[threadIdx.x] = v;
+}
+
+// ---- decoders -------------------------------------------------------------------------------------------
+// conf[t] = max of row t, obs[t] = its first index (one wave per frame)
+__global__ void __launch_bounds__(kThreads) crepe_argmax_kernel(const float* __restrict__ act, int64_t total,
+                                                               float* __restrict__ conf, int32_t* __restrict__ obs) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * (kThreads / 64) + (threadIdx.x >> 6);
+  if (t >= total) return;   // (whole waves leave together; no barrier below)
+  const float* row = act + t * kBinsOut;
+  float best = row[lane];
+  int arg = lane;
+  for (int i = lane + 64; i < kBinsOut; i += 64) {
+    const float v = row[i];
+    if (v > best) { best = v; arg = i; }
+  }
+  for (int d = 32; d > 0; d >>= 1) {
+    const float ob = __shfl_xor(best, d);
+    const int oa = __shfl_xor(arg, d);
+    if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+  }
+  if (lane == 0) {
+    conf[t] = best;
+    obs[t] = arg;
+  }
+}
+
+constexpr int kVitThreads = 384;
+
+// path[t] over the frames of one utterance per workgroup; psi: back pointers [total x 360]
+__global__ void __launch_bounds__(kVitThreads) crepe_viterbi_kernel(const int32_t* __restrict__ obs,
+                                                                   const int64_t* __restrict__ foff,
+                                                                   const double* __restrict__ tab,
+                                                                   uint16_t* __restrict__ psi,
+                                                                   int32_t* __restrict__ path) {
+  __shared__ double delta[2][kBinsOut];
+  const int64_t f0 = foff[blockIdx.x], F = foff[blockIdx.x + 1] - f0;
+  if (F <= 0) return;
+  const int j = threadIdx.x;
+  const bool live = j < kBinsOut;
+  const double e_same = tab[kTabSame], e_other = tab[kTabOther];
+  double trans[kBandW];
+  if (live) {
+#pragma unroll
+    for (int d = 0; d < kBandW; ++d) trans[d] = tab[kTabTrans + j * kBandW + d];   // log A[j - 11 + d][j]
+    delta[0][j] = __dadd_rn(tab[kTabStart], obs[f0] == j ? e_same : e_other);
+  }
+  __syncthreads();
+  for (int64_t t = 1; t < F; ++t) {
+    const double* prev = delta[(t - 1) & 1];
+    if (live) {
+      double best = -INFINITY;
+      int arg = 0;
+      bool any = false;
+#pragma unroll
+      for (int d = 0; d < kBandW; ++d) {
+        const int i = j - kBand + d;
+        if (i < 0 || i >= kBinsOut) continue;
+        const double v = __dadd_rn(prev[i], trans[d]);
+        if (!any || v > best) { best = v; arg = i; any = true; }
+      }
+      delta[t & 1][j] = __dadd_rn(best, obs[f0 + t] == j ? e_same : e_other);
+      psi[(f0 + t) * kBinsOut + j] = static_cast<uint16_t>(arg);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double* last = delta[(F - 1) & 1];
+    int state = 0;
+    for (int i = 1; i < kBinsOut; ++i)
+      if (last[i] > last[state]) state = i;
+    path[f0 + F - 1] = state;
+    for (int64_t t = F - 1; t > 0; --t) {
+      state = psi[(f0 + t) * kBinsOut + state];
+      path[f0 + t - 1] = state;
+    }
+  }
+}
+
+// out[t] = (confidence, 10 * 2^(cents / 1200)) with cents the weighted average over bins [c - 4, c + 5)
+__global__ void __launch_bounds__(kThreads) crepe_cents_kernel(const float* __restrict__ act,
+                                                              const float* __restrict__ conf,
+                                                              const int32_t* __restrict__ centre,
+                                                              const double* __restrict__ tab, int64_t total,
+                                                              double* __restrict__ out) {
+  const int64_t t = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (t >= total) return;
+  const int c = centre[t];
+  const int a = max(0, c - 4), b = min(kBinsOut, c + 5);
+  double ps = 0.0, ws = 0.0;
+  for (int i = a; i < b; ++i) {
+    const double v = static_cast<double>(act[t * kBinsOut + i]);
+    ps = __dadd_rn(ps, __dmul_rn(v, tab[kTabCents + i]));
+    ws = __dadd_rn(ws, v);
+  }
+  const double hz = 10.0 * exp2(ps / ws / 1200.0);
+  out[2 * t] = static_cast<double>(conf[t]);
+  out[2 * t + 1] = isnan(hz) ? 0.0 : hz;
+}
+
+unsigned blocks(int64_t n, int64_t per) { return static_cast<unsigned>((n + per - 1) / per); }
+
+}  // namespace
+
+int crepe_table_doubles() { return kTabCents + kBinsOut; }
+
+int launch_crepe_conv(const float* x, int64_t frames, int T, int step, int lead, int L, int K, const float* w,
+                      const float* b, const float* scale, const float* shift, int N, int flags, float* y,
+                      hipStream_t stream) {
+  if (frames <= 0) return SNF_OK;
+  ConvArgs g;
+  g.x = x; g.w = w; g.b = b; g.scale = scale; g.shift = shift; g.y = y;
+  g.M = frames * T; g.K = K; g.N = N; g.T = T; g.step = step; g.lead = lead; g.L = L; g.flags = flags;
+  g.vec_a = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && K % 4 == 0 && L % 4 == 0 && step % 4 == 0 && lead % 4 == 0;
+  g.vec_b = (reinterpret_cast<uintptr_t>(w) & 15) == 0 && N % 4 == 0;
+  const int64_t tiles_m = (g.M + kBM - 1) / kBM;
+  const int tiles_n = (N + kBN - 1) / kBN;
+  if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "crepe: too many tiles for one launch");
+  hipLaunchKernelGGL(crepe_conv_kernel, dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g,
+                     tiles_n);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+int launch_crepe_frames(const int16_t* wave, const int64_t* soff, const int64_t* foff, int64_t n_utts, int64_t first,
+                        int64_t count, int hop, int center, float* out, hipStream_t stream) {
+  if (count <= 0) return SNF_OK;
+  hipLaunchKernelGGL(crepe_frames_kernel, dim3(static_cast<unsigned>(count)), dim3(kThreads), 0, stream, wave, soff,
+                     foff, n_utts, first, hop, center, out);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+int launch_crepe_decode(const float* act, const int64_t* foff, int64_t n_utts, int64_t total, int viterbi,
+                        const double* tab, float* conf, uint16_t* psi, int32_t* bins, double* out,
+                        hipStream_t stream) {
+  if (total <= 0) return SNF_OK;
+  int32_t* obs = bins;
+  int32_t* path = bins + total;
+  hipLaunchKernelGGL(crepe_argmax_kernel, dim3(blocks(total, kThreads / 64)), dim3(kThreads), 0, stream, act, total,
+                     conf, obs);
+  SNF_HIP_CHECK(hipGetLastError());
+  if (viterbi) {
+    hipLaunchKernelGGL(crepe_viterbi_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(kVitThreads), 0, stream, obs,
+                       foff, tab, psi, path);
+    SNF_HIP_CHECK(hipGetLastError());
+  } else {
+    SNF_HIP_CHECK(hipMemcpyAsync(path, obs, sizeof(int32_t) * total, hipMemcpyDeviceToDevice, stream));
+  }
+  hipLaunchKernelGGL(crepe_cents_kernel, dim3(blocks(total, kThreads)), dim3(kThreads), 0, stream, act, conf, path,
+                     tab, total, out);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+}  // namespace snf

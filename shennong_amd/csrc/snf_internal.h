@@ -402,6 +402,21 @@ int launch_bn_nn_input(const float* logmel, const uint8_t* mask, const int32_t* 
                        const int64_t* roff, int64_t n_utts, int64_t total_rows, int context, const float* hd,
                        float* mean, float* x, hipStream_t stream);
 
+// CREPE pitch kernels (kernels_crepe.hip): see that file's header for the design
+constexpr int kConvNorm = 1, kConvPool = 2, kConvSigmoid = 4;   // epilogue of launch_crepe_conv
+int crepe_table_doubles();   // float64 entries of the decoder's table blob
+// y = epilogue(A w): row (f, t) of A is the run of K floats from (t * step - lead) inside frame f's block of L
+// floats of x, zero outside the block; kConvPool halves the rows (maximum over position pairs)
+int launch_crepe_conv(const float* x, int64_t frames, int T, int step, int lead, int L, int K, const float* w,
+                      const float* b, const float* scale, const float* shift, int N, int flags, float* y,
+                      hipStream_t stream);
+int launch_crepe_frames(const int16_t* wave, const int64_t* soff, const int64_t* foff, int64_t n_utts, int64_t first,
+                        int64_t count, int hop, int center, float* out, hipStream_t stream);
+// bins[2 x total]: first argmax per frame, then the decoded bin; out[total x 2] (confidence, Hertz)
+int launch_crepe_decode(const float* act, const int64_t* foff, int64_t n_utts, int64_t total, int viterbi,
+                        const double* tab, float* conf, uint16_t* psi, int32_t* bins, double* out,
+                        hipStream_t stream);
+
 }  // namespace snf
 
 #endif  // SNF_INTERNAL_H_

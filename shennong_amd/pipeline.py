@@ -18,8 +18,9 @@ be given instead (``warps=...``), not both.  ``get_default_config(with_vtln=...)
 here; build it as ``config['vtln'] = VtlnProcessor().get_params()``.  The sharded entry points
 (:mod:`shennong_amd.distributed`) take precomputed warps only.
 
-Not provided by this pipeline: CREPE pitch; bottleneck features (the processor exists -
-:class:`shennong_amd.processor.bottleneck.BottleneckProcessor` - but is not a pipeline entry yet).
+Not provided by this pipeline: CREPE pitch and bottleneck features (the processors exist -
+:class:`shennong_amd.processor.pitch_crepe.CrepePitchProcessor`,
+:class:`shennong_amd.processor.bottleneck.BottleneckProcessor` - but are not pipeline entries yet).
 """
 
 import os

@@ -17,6 +17,8 @@ _HOME = {
     'DiagUbmProcessor': 'ubm',
     'VtlnProcessor': 'vtln',
     'BottleneckProcessor': 'bottleneck',
+    'CrepePitchProcessor': 'pitch_crepe',
+    'CrepePitchPostProcessor': 'pitch_crepe',
 }
 __all__ = sorted(_HOME)
 
