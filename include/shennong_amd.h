@@ -508,6 +508,30 @@ int snf_crepe_forward(int device_id, const int16_t* d_wave, const int64_t* h_sam
 int snf_crepe_decode(int device_id, const float* d_activation, const int64_t* h_frame_offsets, int64_t n_utts,
                      int32_t viterbi, const double* d_tables, double* d_out, int32_t* d_bins, void* stream);
 
+/* ---- framed one-hot labels (reference processor/onehot.py, FramedOneHotProcessor) -------------------
+ * Per-frame labels of a batch of time alignments, one call for the whole batch.  Alignment a holds segments
+ * [h_segment_offsets[a], h_segment_offsets[a + 1]) of h_offsets (float64 seconds, not decreasing) and
+ * h_token_ids (in [0, h_num_tokens[a])); sample i of it sits at i / sample_rate + h_first_onsets[a] (float64,
+ * one division then one addition) and carries the first token whose offset is greater than that time - the
+ * last token when rounding leaves none (the reference's walk, alignment.py:321-337, ends in an IndexError
+ * there).  Frame f covers samples [f * frame_shift, f * frame_shift + frame_length); h_num_frames[a] of them
+ * must fit in the h_num_samples[a] samples.  A frame takes the token all its samples carry, or else the token
+ * with the largest window weight: the float32 sum of the window coefficients of its samples, added in sample
+ * order from zero, one sum per token; an exact tie goes to the token that appears first in the frame
+ * (processor/onehot.py:235-254).  The window is snf_window_function's table of frame_length coefficients
+ * (ones for a length of 1, and of 2 when the window has zeros at both ends, reference window.py:97-105).
+ * d_winners[total_frames] int32: the token id of every frame; d_onehot: the dense rows, alignment a's
+ * [h_num_frames[a] x h_num_tokens[a]] uint8 (0 / 1) from byte h_row_offsets[a] on - h_row_offsets[n + 1], every
+ * entry a multiple of 16, entry a + 1 at least frames x tokens bytes after entry a; the bytes between the last
+ * row and the next entry are zeroed.  d_onehot holds h_row_offsets[n] bytes and is 16-byte aligned.  kernel_ms
+ * (may be NULL): device time of the kernels, from events.  Three launches whatever the batch. */
+int snf_framed_onehot(int device_id, double sample_rate, int32_t frame_length, int32_t frame_shift,
+                      int32_t window_type, float blackman_coeff, int64_t n_alignments,
+                      const int64_t* h_segment_offsets, const double* h_first_onsets, const double* h_offsets,
+                      const int32_t* h_token_ids, const int64_t* h_num_samples, const int64_t* h_num_frames,
+                      const int32_t* h_num_tokens, const int64_t* h_row_offsets, int32_t* d_winners,
+                      uint8_t* d_onehot, float* kernel_ms, void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

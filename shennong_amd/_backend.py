@@ -44,7 +44,7 @@ EXPORTS = [
     'snf_gmm_selection_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
     'snf_affine_apply_segments', 'snf_vtln_gram_rows', 'snf_dense_layer', 'snf_bottleneck_vad',
     'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward', 'snf_crepe_conv',
-    'snf_crepe_forward', 'snf_crepe_decode']
+    'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -175,6 +175,8 @@ def lib():
         L.snf_crepe_conv.argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp]
         L.snf_crepe_forward.argtypes = [i32, vp, pi64, i64, i32, i32, pi32, C.POINTER(vp), vp, vp]
         L.snf_crepe_decode.argtypes = [i32, vp, pi64, i64, i32, vp, vp, vp, vp]
+        L.snf_framed_onehot.argtypes = [i32, C.c_double, i32, i32, i32, f32, i64, pi64, pf64, pf64, pi32, pi64, pi64,
+                                        pi32, pi64, vp, vp, pf, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)

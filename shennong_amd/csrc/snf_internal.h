@@ -417,6 +417,23 @@ int launch_crepe_decode(const float* act, const int64_t* foff, int64_t n_utts, i
                         const double* tab, float* conf, uint16_t* psi, int32_t* bins, double* out,
                         hipStream_t stream);
 
+// Framed one-hot labels (kernels_onehot.hip): see that file's header for the design.  Device pointers; the
+// caller (capi_onehot.hip) has checked on the host everything the kernels index with.
+constexpr int kOneHotMaxFrameLength = 8192;   // samples per frame: the window sits in LDS
+struct OneHotBatch {
+  int64_t n_ali, n_seg, total_frames, total_bytes;   // total_bytes: of the dense rows, a multiple of 16
+  int frame_length, frame_shift;
+  double rate;
+  const int64_t *seg_off, *frame_off, *row_off, *nsamples;   // [n_ali + 1] x 3, [n_ali]
+  const double *onset0, *offsets;                             // [n_ali], [n_seg]
+  const int32_t *ids, *ntokens;                               // [n_seg], [n_ali]
+  const float* window;                                        // [frame_length]
+  int64_t* ends;                                              // [n_seg] scratch: first sample past every segment
+  int32_t* winner;                                            // [total_frames]
+  uint8_t* rows;                                              // [total_bytes]
+};
+int launch_framed_onehot(const OneHotBatch& batch, hipStream_t stream);
+
 }  // namespace snf
 
 #endif  // SNF_INTERNAL_H_

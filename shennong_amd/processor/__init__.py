@@ -19,6 +19,8 @@ _HOME = {
     'BottleneckProcessor': 'bottleneck',
     'CrepePitchProcessor': 'pitch_crepe',
     'CrepePitchPostProcessor': 'pitch_crepe',
+    'OneHotProcessor': 'onehot',
+    'FramedOneHotProcessor': 'onehot',
 }
 __all__ = sorted(_HOME)
 
