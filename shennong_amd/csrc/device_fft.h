@@ -204,6 +204,26 @@ __device__ __forceinline__ float dpp_mov(float old, float v) {
                                                                __builtin_bit_cast(int, v), CTRL, 0xf,
                                                                0xf, BOUND));
 }
+// Lane 0 of every 16-lane row: v[j] := v[j - 1], v[0] := first; the other lanes keep v.  With v[j] a row_ror:1
+// of element j this is the left neighbour across the seam between two elements (lane 0's neighbour is lane 15 of
+// the element before).  Thirteen plain moves under an exec mask of the rows' first lanes instead of thirteen
+// v_cndmask_b32 on a scalar mask, which issue at half rate.  Exec is saved and restored by SALU writes (no wait
+// states towards the vector instructions behind them); `row_heads` is 0x0001000100010001.
+__device__ __forceinline__ void row_head_carry13(float (&v)[13], float first, unsigned long long row_heads) {
+  unsigned long long saved;
+  asm volatile(
+      "s_and_saveexec_b64 %[sv], %[m]\n"
+      "v_mov_b32 %[v12], %[v11]\n v_mov_b32 %[v11], %[v10]\n v_mov_b32 %[v10], %[v9]\n v_mov_b32 %[v9], %[v8]\n"
+      "v_mov_b32 %[v8], %[v7]\n v_mov_b32 %[v7], %[v6]\n v_mov_b32 %[v6], %[v5]\n v_mov_b32 %[v5], %[v4]\n"
+      "v_mov_b32 %[v4], %[v3]\n v_mov_b32 %[v3], %[v2]\n v_mov_b32 %[v2], %[v1]\n v_mov_b32 %[v1], %[v0]\n"
+      "v_mov_b32 %[v0], %[f]\n"
+      "s_mov_b64 exec, %[sv]"
+      : [sv] "=&s"(saved), [v0] "+v"(v[0]), [v1] "+v"(v[1]), [v2] "+v"(v[2]), [v3] "+v"(v[3]), [v4] "+v"(v[4]),
+        [v5] "+v"(v[5]), [v6] "+v"(v[6]), [v7] "+v"(v[7]), [v8] "+v"(v[8]), [v9] "+v"(v[9]), [v10] "+v"(v[10]),
+        [v11] "+v"(v[11]), [v12] "+v"(v[12])
+      : [m] "s"(row_heads), [f] "v"(first)
+      : "scc");
+}
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short short2v __attribute__((ext_vector_type(2)));
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));  // output rows are 4-byte aligned

@@ -61,6 +61,17 @@ constexpr int kTileBytes = 16 * kTileRow * 8;  // wave-private LDS per frame (21
 // fbank512_kernel (same key per frame, same generator: bit-identical features from either kernel); the key
 // of a frame comes from a table made once per call (launch_build_frame_noise) and is prefetched with the
 // frame's first-sample index.
+// Trimming pass (NJ = 13 only; profiles/NOTEBOOK.md 4.1d, profiles/fbank512b_prune_*): work the result does not
+// need.  (i) lane 0's left neighbour comes from thirteen exec-masked moves behind the thirteen row rotations
+// (row_head_carry13) instead of thirteen v_cndmask_b32 on a scalar mask, which issue at half rate.  (ii) the
+// lane's operand start and first bin of the mel phase are read from the table once, not per set (each was an
+// LDS round trip the wave sat through), and the test for a fourth block of a split group stands outside the
+// loop over the four bins (four branches and a dozen register copies per set less).  The in_window selects of
+// the frame sum were already folded for j < 12 by the compiler.  The NJ = 16 forms keep their table reads (no
+// register to spare).  NOT shipped: pass 1 through fft16_lf_head<13> (z[13..15] are the padding of the
+// 512-point window).  Without the `+ 0` of the full first layer the compiler contracts other multiply / add
+// pairs around the butterflies than it does in fbank512_kernel: 4.5 % of the outputs differed in the last bits
+// (up to 3e-5), with and without the forwarded products pinned (tools/experiments/fbank512b_prune_pass1.diff).
 template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER>
 __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512Params p, const BatchArgs b,
                                                                   float* __restrict__ out,
@@ -91,13 +102,20 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
   // floats past the power tile with zero weights: LDS keeps what the previous kernel left there (see
   // fbank512_kernel).  Zero it once.
   tile[l * kTileRow + 16] = make_float2(0.0f, 0.0f);
-  // MFMA view of the wave: lane = 4 b + j, block b, frame j of the set.  Where the lane's B operands start,
-  // the first of the 4 bins it stores and the 0 / 1 factors of the partial sums of a split group are read
-  // from the table where they are used (five registers less through the transform).
+  // MFMA view of the wave: lane = 4 b + j, block b, frame j of the set.  The 0 / 1 factors of the partial sums
+  // of a split group are read from the table where they are used (three registers less through the transform).
   const int mj = lane & 3;
   const float* __restrict__ mm_lane = tab + p.off_mm_lane + lane;
   const float* __restrict__ mtile =
       reinterpret_cast<const float*>(smem + tab_bytes + (wid * 4 + mj) * kTileBytes) + mj * 16;
+  // (NJ = 13 reads the two the mel phase opens with once: inside the loop each was an LDS round trip that the
+  // wave sat through at the head of the chain and in front of the store.  The NJ = 16 forms have no register
+  // to spare for them.)
+  int mm_start_once = 0, mm_out_once = 0;
+  if (NJ == 13) {
+    mm_start_once = reinterpret_cast<const int*>(mm_lane)[0];
+    mm_out_once = reinterpret_cast<const int*>(mm_lane)[64];
+  }
 
   const float win_len_f = static_cast<float>(p.win_len), inv_win_len = 1.0f / win_len_f;
   const int64_t n_sets = (b.total_frames + 3) >> 2;
@@ -205,6 +223,14 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     float2 z[16];
     float e_raw = 0.0f, e_post = 0.0f;
     float rot_prev = xe[0] + neg_mean;  // lane 0, j = 0: x[-1] := x[0] (Kaldi Preemphasize)
+    // NJ = 13: the left neighbours of all elements first, lane 0's taken from the element before by
+    // exec-masked moves (row_head_carry13) instead of a select on a scalar mask per element
+    float left[13];
+    if (NJ == 13) {
+#pragma unroll
+      for (int j = 0; j < 13; ++j) left[j] = dpp_row_ror<0x121>(xo[j] + neg_mean);
+      row_head_carry13(left, rot_prev, 0x0001000100010001ull);
+    }
 #pragma unroll
     for (int jj = 0; jj < 16; jj += 2) {
       float4 w4;
@@ -215,9 +241,14 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
         if (j < NJ) {
           const float ae = xe[j] + neg_mean, ao = xo[j] + neg_mean;
           // the left neighbour x[2n-1] is the odd sample of lane l - 1 (same j), or lane 15 of j - 1
-          const float rot = dpp_row_ror<0x121>(ao);
-          const float ap = l == 0 ? rot_prev : rot;
-          rot_prev = rot;
+          float ap;
+          if (NJ == 13) {
+            ap = left[j < 13 ? j : 0];
+          } else {
+            const float rot = dpp_row_ror<0x121>(ao);
+            ap = l == 0 ? rot_prev : rot;
+            rot_prev = rot;
+          }
           const float2 w = (j & 1) ? make_float2(w4.z, w4.w) : make_float2(w4.x, w4.y);
           if (ENERGY == 1 && in_window(j)) e_raw += ae * ae + ao * ao;
           const float ye = (ae - p.preemph * ap) * w.x;
@@ -332,7 +363,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     {
       // ---- F: mel filterbank on the matrix pipe (see fbank512_kernel) -------------------------------
       const bool mvalid = set * 4 + mj <= last_frame;
-      const int mm_start = reinterpret_cast<const int*>(mm_lane)[0];
+      const int mm_start = NJ == 13 ? mm_start_once : reinterpret_cast<const int*>(mm_lane)[0];
       const float4* __restrict__ bsrc = reinterpret_cast<const float4*>(mtile + mm_start);
       const float4* __restrict__ asrc = t_mm_a + lane;
       f32x4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -374,17 +405,28 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
       float mel[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) mel[i] = acc0[i] + acc1[i];
-      const int mm_out = reinterpret_cast<const int*>(mm_lane)[64];
+      const int mm_out = NJ == 13 ? mm_out_once : reinterpret_cast<const int*>(mm_lane)[64];
       // a wide group is split over up to 4 neighbouring blocks of one 16-lane row: the first block adds
       // the sums of the others (0 / 1 factors per lane; one v_fmac_f32 with a DPP row shift each)
       if (p.mm_levels > 1) {
         const float mm_f1 = mm_lane[128], mm_f2 = mm_lane[192], mm_f3 = mm_lane[256];
+        // (the test for a fourth block outside the loop over the bins: inside, the compiler kept four
+        // branches and a dozen register copies between them)
+        if (p.mm_levels > 3) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float own = mel[i];
-          fmac_row_shl<4>(mel[i], own, mm_f1);
-          fmac_row_shl<8>(mel[i], own, mm_f2);
-          if (p.mm_levels > 3) fmac_row_shl<12>(mel[i], own, mm_f3);
+          for (int i = 0; i < 4; ++i) {
+            const float own = mel[i];
+            fmac_row_shl<4>(mel[i], own, mm_f1);
+            fmac_row_shl<8>(mel[i], own, mm_f2);
+            fmac_row_shl<12>(mel[i], own, mm_f3);
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float own = mel[i];
+            fmac_row_shl<4>(mel[i], own, mm_f1);
+            fmac_row_shl<8>(mel[i], own, mm_f2);
+          }
         }
       }
       const int mel_col = (KIND == SNF_KIND_FBANK && p.use_energy && !p.htk_compat) ? 1 : 0;
