@@ -446,13 +446,14 @@ int snf_plan_run_batch_device(snf_plan* plan, const int16_t* d_wave, const int64
     if (plan->chain_deltas) {
       const bool build_tiles = oc.tile_cols != feat_cols;
       if ((rc = ms.tile.ensure(4 * sizeof(int64_t) * static_cast<size_t>(total_frames / 32 + 2)))) return rc;
+      const char* delta_launched = nullptr;
       if ((rc = launch_deltas(plan->dp, feat_out, feat_cols, oc.foff.as<int64_t>(), n_utts, total_frames,
-                              d_out, ms.tile.as<int64_t>(), build_tiles, s)))
+                              d_out, ms.tile.as<int64_t>(), build_tiles, s, &delta_launched)))
         return rc;
       // (the tile records are cached: complete before a later call on another stream may use them)
       if (build_tiles && !own_stream) SNF_HIP_CHECK(hipStreamSynchronize(s));
       oc.tile_cols = feat_cols;
-      c.mark("delta_kernel");
+      if (delta_launched) c.mark(delta_launched);
     }
   }
   if (own_stream) SNF_HIP_CHECK(hipStreamSynchronize(s));

@@ -45,23 +45,26 @@ int snf_post_run_batch_device(snf_plan* plan, const float* d_in, int32_t in_cols
   if (plan->kind == SNF_KIND_DELTA) {
     if (in_cols <= 0) return set_error(SNF_E_INVALID, "in_cols must be positive");
     if ((rc = plan->post_s.tile.ensure(4 * sizeof(int64_t) * static_cast<size_t>(total_frames / 32 + 2)))) return rc;
+    const char* launched = nullptr;
     if ((rc = launch_deltas(plan->dp, d_in, in_cols, plan->oc.foff.as<int64_t>(), n_utts,
-                            total_frames, d_out, plan->post_s.tile.as<int64_t>(), !same_table, s)))
+                            total_frames, d_out, plan->post_s.tile.as<int64_t>(), !same_table, s,
+                            &launched)))
       return rc;
     // (the tile records are complete before a later call on another stream may use them)
     if (!same_table && !own_stream) SNF_HIP_CHECK(hipStreamSynchronize(s));
     plan->oc.tile_cols = in_cols;
-    if (own_stream) mark_kernel(plan, "delta_kernel");
+    if (own_stream && launched) mark_kernel(plan, launched);
   } else if (plan->kind == SNF_KIND_PITCH_POST) {
     if (in_cols != 2)
       return set_error(SNF_E_INVALID, "data shape must be (_, 2), but it is (_, " +
                                           std::to_string(in_cols) + ")");
     if (plan->ppost.o.delta_pitch_noise_stddev != 0.0f)
       plan->ppost.seed = plan->o.seed + 0x9E3779B97F4A7C15ull * (named_call ? named_call : ++plan->noise_calls);
+    const char* launched = nullptr;
     if ((rc = launch_pitch_post(plan->ppost, d_in, plan->oc.foff.as<int64_t>(), n_utts,
-                                total_frames, d_out, s)))
+                                total_frames, d_out, s, &launched)))
       return rc;
-    if (own_stream) mark_kernel(plan, "pitch_post_kernel");
+    if (own_stream && launched) mark_kernel(plan, launched);
   } else if (plan->kind == SNF_KIND_VAD) {
     if (in_cols <= 0) return set_error(SNF_E_INVALID, "in_cols must be positive");
     if ((rc = plan->post_s.stats.ensure(sizeof(float) * static_cast<size_t>(n_utts)))) return rc;
@@ -144,10 +147,11 @@ int snf_cmvn_accumulate_device(snf_plan* plan, const float* d_in, int32_t cols,
   std::vector<int64_t> foff(frame_offsets, frame_offsets + n_utts + 1);
   if ((rc = plan->oc.foff.upload(foff, s))) return rc;
   begin_timing(plan);
+  const char* launched = nullptr;
   if ((rc = launch_cmvn_stats(d_in, cols, plan->oc.foff.as<int64_t>(), d_weights, n_utts,
-                              plan->post_s.stats.as<double>(), s)))
+                              plan->post_s.stats.as<double>(), s, &launched)))
     return rc;
-  mark_kernel(plan, "cmvn_stats_kernel");
+  if (launched) mark_kernel(plan, launched);
   std::vector<double> per_utt(blk * static_cast<size_t>(n_utts));
   SNF_HIP_CHECK(hipMemcpyAsync(per_utt.data(), plan->post_s.stats.p, sizeof(double) * per_utt.size(),
                                hipMemcpyDeviceToHost, s));

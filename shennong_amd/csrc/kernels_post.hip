@@ -794,7 +794,8 @@ __global__ __launch_bounds__(256) void delta_flat_o2w2_kernel(
 
 int launch_deltas(const DeltaParams& p, const float* in, int in_cols, const int64_t* frame_offsets,
                   int64_t n_utts, int64_t total_frames, float* out, int64_t* tile_info, bool build_info,
-                  hipStream_t stream) {
+                  hipStream_t stream, const char** launched) {
+  if (launched) *launched = nullptr;
   const int64_t total = total_frames * in_cols;
   if (total <= 0) return SNF_OK;
   const int halo = p.order * p.window;
@@ -821,7 +822,10 @@ int launch_deltas(const DeltaParams& p, const float* in, int in_cols, const int6
     else SNF_FLAT(43);
 #undef SNF_FLAT
     SNF_HIP_CHECK(hipGetLastError());
-    if (aligned16) return SNF_OK;
+    if (aligned16) {
+      if (launched) *launched = "delta_flat_o2w2_kernel";
+      return SNF_OK;
+    }
   }
   const size_t lds = 2 * sizeof(int) * kDeltaRows + sizeof(float) * ((p.n_scales + 3) & ~3) +
                      sizeof(float) * static_cast<size_t>(kDeltaRows + 2 * halo) * in_cols;
@@ -836,6 +840,7 @@ int launch_deltas(const DeltaParams& p, const float* in, int in_cols, const int6
       hipLaunchKernelGGL((delta_tiled_fixed_kernel<1, 2>), dim3(tiles), dim3(256), lds_fixed, stream, p,
                          in, in_cols, frame_offsets, n_utts, total_frames, out);
     SNF_HIP_CHECK(hipGetLastError());
+    if (launched) *launched = "delta_tiled_fixed_kernel";
     return SNF_OK;
   }
   if (lds <= 48 * 1024 && in_cols <= 256) {
@@ -844,6 +849,7 @@ int launch_deltas(const DeltaParams& p, const float* in, int in_cols, const int6
                        dim3(256), lds, stream, p, in, in_cols, halo, frame_offsets, n_utts,
                        total_frames, out);
     SNF_HIP_CHECK(hipGetLastError());
+    if (launched) *launched = "delta_tiled_kernel";
     return SNF_OK;
   }
   const int threads = 256;
@@ -851,6 +857,7 @@ int launch_deltas(const DeltaParams& p, const float* in, int in_cols, const int6
                      dim3(threads), 0, stream, p, in, in_cols, frame_offsets, n_utts, total_frames,
                      out);
   SNF_HIP_CHECK(hipGetLastError());
+  if (launched) *launched = "delta_kernel";
   return SNF_OK;
 }
 
@@ -871,6 +878,17 @@ __device__ __forceinline__ float nccf_to_pov(float n) {
   return static_cast<float>(1.0 / (1.0 + exp(-1.0 * static_cast<double>(r))));
 }
 
+// Log pitch.  The reference takes Kaldi's Log(float), glibc's logf, which is correctly rounded in all but a handful
+// of arguments; the device's logf (log2 in hardware, then the product by ln 2) errs by up to 2 ulp at 50 - 400 Hz,
+// which the float64 statement tells apart (tests/test_post_routes_gpu.py).  The double logarithm rounded once gives
+// the reference's value.  pitch_post_tiled_kernel evaluates it once per frame, next to the four double exponentials
+// of nccf_to_pov (0.0284 -> 0.0295 ms on 300 000 frames); pitch_post_kernel, the route of windows too long for LDS,
+// pays for it at every window position like it does for the exponentials (0.46 -> 0.71 ms on 1 000 utterances of 300
+// frames with a left context of 6 000).
+__device__ __forceinline__ float log_pitch_of(float hz) {
+  return static_cast<float>(log(static_cast<double>(hz)));
+}
+
 __global__ void pitch_post_kernel(const PitchPostParams p, const float* __restrict__ in,
                                   const int64_t* __restrict__ frame_offsets, const int64_t n_utts,
                                   const int64_t total_frames, float* __restrict__ out) {
@@ -881,7 +899,7 @@ __global__ void pitch_post_kernel(const PitchPostParams p, const float* __restri
   const snf_pitch_post_options& o = p.o;
   float* __restrict__ row = out + g * p.ndims;
   int idx = 0;
-  const float nccf = in[g * 2], log_pitch = logf(in[g * 2 + 1]);
+  const float nccf = in[g * 2], log_pitch = log_pitch_of(in[g * 2 + 1]);
   if (o.add_pov_feature) row[idx++] = o.pov_scale * nccf_to_pov_feature(nccf) + o.pov_offset;
   if (o.add_normalized_log_pitch) {
     int64_t wb = g - o.normalization_left_context, we = g + o.normalization_right_context + 1;
@@ -889,7 +907,7 @@ __global__ void pitch_post_kernel(const PitchPostParams p, const float* __restri
     if (we > f1) we = f1;
     double sum_pov = 0.0, sum_lp = 0.0;
     for (int64_t t = wb; t < we; ++t) {
-      const float pov = nccf_to_pov(in[t * 2]), lp = logf(in[t * 2 + 1]);
+      const float pov = nccf_to_pov(in[t * 2]), lp = log_pitch_of(in[t * 2 + 1]);
       sum_pov += pov;
       sum_lp += pov * lp;
     }
@@ -910,7 +928,7 @@ __global__ void pitch_post_kernel(const PitchPostParams p, const float* __restri
       int64_t t = g + j;
       t = t < lo ? lo : (t > hi ? hi : t);
       const float s = static_cast<float>(j) * inv;
-      if (s != 0.0f) acc += s * logf(in[t * 2 + 1]);
+      if (s != 0.0f) acc += s * log_pitch_of(in[t * 2 + 1]);
     }
     float noise = 0.0f;
     if (o.delta_pitch_noise_stddev != 0.0f)
@@ -941,7 +959,7 @@ __global__ __launch_bounds__(kPostRows) void pitch_post_tiled_kernel(
     float pov = 0.0f, lp = 0.0f;
     if (t >= 0 && t < total_frames) {
       pov = nccf_to_pov(in[t * 2]);
-      lp = logf(in[t * 2 + 1]);
+      lp = log_pitch_of(in[t * 2 + 1]);
     }
     s_pov[i] = pov;
     s_lp[i] = lp;
@@ -995,7 +1013,9 @@ __global__ __launch_bounds__(kPostRows) void pitch_post_tiled_kernel(
 }
 
 int launch_pitch_post(const PitchPostParams& p, const float* in, const int64_t* frame_offsets,
-                      int64_t n_utts, int64_t total_frames, float* out, hipStream_t stream) {
+                      int64_t n_utts, int64_t total_frames, float* out, hipStream_t stream,
+                      const char** launched) {
+  if (launched) *launched = nullptr;
   if (total_frames <= 0) return SNF_OK;
   {
     int halo_l = p.o.normalization_left_context, halo_r = p.o.normalization_right_context;
@@ -1004,12 +1024,14 @@ int launch_pitch_post(const PitchPostParams& p, const float* in, const int64_t* 
     if (halo_l < 0) halo_l = 0;
     if (halo_r < 0) halo_r = 0;
     const size_t lds = sizeof(float) * 2 * static_cast<size_t>(kPostRows + halo_l + halo_r);
-    if (lds <= 48 * 1024) {
+    // (SNF_PITCH_POST_PER_FRAME: the kernel of the long windows on any window - the two are compared bit for bit)
+    if (lds <= 48 * 1024 && !getenv("SNF_PITCH_POST_PER_FRAME")) {
       hipLaunchKernelGGL(pitch_post_tiled_kernel,
                          dim3(static_cast<unsigned>((total_frames + kPostRows - 1) / kPostRows)),
                          dim3(kPostRows), lds, stream, p, in, halo_l, halo_r, frame_offsets, n_utts,
                          total_frames, out);
       SNF_HIP_CHECK(hipGetLastError());
+      if (launched) *launched = "pitch_post_tiled_kernel";
       return SNF_OK;
     }
   }
@@ -1018,6 +1040,7 @@ int launch_pitch_post(const PitchPostParams& p, const float* in, const int64_t* 
                      dim3(static_cast<unsigned>((total_frames + threads - 1) / threads)),
                      dim3(threads), 0, stream, p, in, frame_offsets, n_utts, total_frames, out);
   SNF_HIP_CHECK(hipGetLastError());
+  if (launched) *launched = "pitch_post_kernel";
   return SNF_OK;
 }
 
@@ -1151,12 +1174,15 @@ __global__ __launch_bounds__(256) void cmvn_stats_wide_kernel(const float* __res
 }
 
 int launch_cmvn_stats(const float* in, int in_cols, const int64_t* frame_offsets,
-                      const float* weights, int64_t n_utts, double* stats, hipStream_t stream) {
+                      const float* weights, int64_t n_utts, double* stats, hipStream_t stream,
+                      const char** launched) {
+  if (launched) *launched = nullptr;
   if (n_utts <= 0) return SNF_OK;
   if (in_cols > 256) {
     hipLaunchKernelGGL(cmvn_stats_wide_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(256), 0, stream,
                        in, in_cols, frame_offsets, weights, stats);
     SNF_HIP_CHECK(hipGetLastError());
+    if (launched) *launched = "cmvn_stats_wide_kernel";
     return SNF_OK;
   }
   const int R = 256 / in_cols > 0 ? 256 / in_cols : 1;
@@ -1164,6 +1190,7 @@ int launch_cmvn_stats(const float* in, int in_cols, const int64_t* frame_offsets
   hipLaunchKernelGGL(cmvn_stats_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(256), lds, stream,
                      in, in_cols, frame_offsets, weights, stats);
   SNF_HIP_CHECK(hipGetLastError());
+  if (launched) *launched = "cmvn_stats_kernel";
   return SNF_OK;
 }
 

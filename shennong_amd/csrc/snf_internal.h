@@ -199,10 +199,12 @@ int launch_rasta(float* mel, const BatchArgs& b, int num_bins, hipStream_t strea
 int launch_plp_tail(const PlpParams& p, const BatchArgs& b, const float* mel, const double* energy,
                     float* out, hipStream_t stream);
 // `tile_info`: scratch of 4 (total_frames / 32 + 2) int64 (nullptr: per-element kernels only), rebuilt
-// from the offsets table when `build_info` is set (the caller keeps it while the table stays the same)
+// from the offsets table when `build_info` is set (the caller keeps it while the table stays the same).
+// `launched`: receives the name of the kernel that computes the rows (delta_flat_o2w2_kernel,
+// delta_tiled_fixed_kernel, delta_tiled_kernel or delta_kernel; nullptr: nothing was launched)
 int launch_deltas(const DeltaParams& p, const float* in, int in_cols, const int64_t* frame_offsets,
                   int64_t n_utts, int64_t total_frames, float* out, int64_t* tile_info, bool build_info,
-                  hipStream_t stream);
+                  hipStream_t stream, const char** launched = nullptr);
 
 
 // ---- register-resident 512-point fast path (kernels_fbank512.hip) ----------------------------------
@@ -332,8 +334,10 @@ int launch_pitch(const PitchDevTables& t, const PitchBatch& b, const PitchScratc
 int launch_vad(const snf_vad_options& o, const float* in, int in_cols, const int64_t* frame_offsets,
                int64_t n_utts, int64_t total_frames, float* thr_scratch, float* out,
                hipStream_t stream);
+// `launched`: cmvn_stats_kernel or cmvn_stats_wide_kernel (nullptr: nothing was launched)
 int launch_cmvn_stats(const float* in, int in_cols, const int64_t* frame_offsets,
-                      const float* weights, int64_t n_utts, double* stats, hipStream_t stream);
+                      const float* weights, int64_t n_utts, double* stats, hipStream_t stream,
+                      const char** launched = nullptr);
 int launch_cmvn_apply(const float* in, int in_cols, const int64_t* frame_offsets, int64_t n_utts,
                       int64_t max_frames, const int32_t* group, const float* norm, int scale_it,
                       float* out, hipStream_t stream);
@@ -351,7 +355,8 @@ struct PitchPostParams {
   unsigned long long seed;
 };
 int launch_pitch_post(const PitchPostParams& p, const float* in, const int64_t* frame_offsets,
-                      int64_t n_utts, int64_t total_frames, float* out, hipStream_t stream);
+                      int64_t n_utts, int64_t total_frames, float* out, hipStream_t stream,
+                      const char** launched = nullptr);  // pitch_post_tiled_kernel or pitch_post_kernel
 
 // GMM kernels (kernels_gmm.hip): see that file's header for the design
 int64_t gmm_stats_chunks(int64_t F, int C, int D);
