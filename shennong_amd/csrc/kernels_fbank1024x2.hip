@@ -1,19 +1,19 @@
 // Register-resident spectrogram / filterbank / MFCC / PLP-mel kernel for frames that pad to 1024 samples
 // (25 ms windows at 22.05 and 32 kHz; the reference resamples nothing, it frames whatever rate the file
-// has: shennong/processor/base.py:408-436), on gfx950.  Round 6: these frames used to run as the
-// 2048-point transform of the zero-extended frame (kernels_fbank2048.hip: twice the arithmetic a frame
-// needs, and odd window lengths - 551 samples at 22.05 kHz - fell to the generic kernel).
+// has: shennong/processor/base.py:408-436), on gfx950.  Any window length from 65 to 1024 samples runs, odd
+// ones too (551 samples at 22.05 kHz).
 //
 //   wave64 = TWO frames of one utterance, packed as one complex signal z[n] = x_a[n] + i x_b[n], n < 1024.
-//   The three register passes of the long-frame kernel (16 x 4 x 16 around two LDS transposes) transform
-//   it; the spectra separate without a twiddle:
+//   The 1024-point transform this kernel shares with kernels_fbank2048.hip (device_fft1024.h: three register
+//   passes, 16 x 4 x 16, around two LDS transposes) transforms it; the spectra separate without a twiddle:
 //       X_a[k] = (Z[k] + conj Z[1024 - k]) / 2,   X_b[k] = (Z[k] - conj Z[1024 - k]) / 2i,   k <= 512.
 //   A  lane L loads x[L + 64 j] of both frames (16-bit loads, 128 contiguous bytes per wave instruction;
 //      the next pair's samples are requested when this pair's transform is done); per frame: DC removal
 //      over the wave, pre-emphasis (left neighbour through ds_bpermute), window
-//   B-D as kernels_fbank2048.hip (same tables, same index maps: tools/model_fbank2048.py)
+//   B-D cfft1024_passes (its tables and index maps: device_fft1024.h, tools/model_fbank2048.py)
 //   E  the upper half of Z meets its partner through LDS; two power spectra (513 bins each) to LDS
-//   F  the epilogue of the long-frame kernel, once per frame
+//   F  the epilogue of kernels_fbank2048.hip for both frames: mel rounds of its own (a filter's weights are
+//      fetched once for the two frames), the energy and MFCC tail of device_fft1024.h
 // Pairs are formed INSIDE an utterance (PairRec: frames 2 m and 2 m + 1; an odd last frame is transformed
 // alone, its partner is zero), so the features of an utterance do not depend on what else is in the batch.
 // The two real transforms share their roundings: the error floor of both spectra is set by the louder
@@ -28,14 +28,14 @@
 
 #include "snf_internal.h"
 #include "device_fft.h"
+#include "device_fft1024.h"
 
 namespace snf {
 
 namespace {
 
-constexpr int kPairWaves = 16;                 // one workgroup per CU: 16 pairs in flight
-constexpr int kPairBufBytes = 1088 * 8;        // wave-private LDS: 16 rows x (64 + 4) complex = 64 rows x 17
 // table blob (float2 units): window (w, w) [64][18] | W1024^(L k1) [64][18] | W64^(b c) [4][16 + 2]
+// (fft1024_twiddle_tables)
 constexpr int kOffWin = 0, kOffTw1 = 64 * 18, kOffTw2 = 2 * 64 * 18;
 constexpr int kPairTableFloat2 = kOffTw2 + 4 * 18;
 constexpr int kPairTableBytes = kPairTableFloat2 * 8;
@@ -43,29 +43,12 @@ constexpr int kSpecB = 544;                    // float offset of frame b's powe
 constexpr int kMelBuf = 1152;                  // ... of the log-mel energies (MFCC), 128 per frame
 constexpr float kSplitRatio = 8.0f;            // windowed-energy ratio beyond which a pair is split
 
-__device__ __forceinline__ float readlane_f(float v, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-__device__ __forceinline__ float wave_sum64(float v) {
-  v = row_sum16(v);
-  return (readlane_f(v, 0) + readlane_f(v, 16)) + (readlane_f(v, 32) + readlane_f(v, 48));
-}
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<int>(v));
-  const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<int>(v >> 32));
-  return static_cast<int64_t>((static_cast<unsigned long long>(hi) << 32) | lo);
-}
-// value of `v` in lane (lane - 1) mod 64 (a DPP move with wave_ror:1: kernels_fbank2048.hip)
-__device__ __forceinline__ float from_left_lane(float v, int) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x13C, 0xf, 0xf, false));
-}
-
 }  // namespace
 
 // NJ: element rows a lane can hold inside the window, ceil(win_len / 64): 9 covers 25 ms at 22.05 kHz,
 // 13 the same at 32 kHz, 16 any window up to 1024 samples.
 template <int NJ, int KIND, bool DITHER, bool SNIP>
-__global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
+__global__ __launch_bounds__(kLongWaves * 64) void fbank1024x2_kernel(
     const MelParams p, const BatchArgs b, const float2* __restrict__ gtab, const float split_ratio,
     float* __restrict__ out, const int out_cols, double* __restrict__ energy_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -73,16 +56,15 @@ __global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
   for (int i = threadIdx.x; i < kPairTableFloat2; i += blockDim.x) tab[i] = gtab[i];
   __syncthreads();  // the only workgroup-wide barrier: the waves are independent from here on
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  float2* buf = reinterpret_cast<float2*>(smem + kPairTableBytes + wid * kPairBufBytes);
+  float2* buf = reinterpret_cast<float2*>(smem + kPairTableBytes + wid * kLongBufBytes);
   float* ps = reinterpret_cast<float*>(buf);   // power spectra: frame a at 0, frame b at kSpecB
   // (the mel phase multiplies a few floats beyond a spectrum by zero weights, and the padding slots of the
   // transposes are never written: clear the wave's buffer once - 0 * NaN = NaN)
-  for (int i = lane; i < kPairBufBytes / 8; i += 64) buf[i] = make_float2(0.0f, 0.0f);
+  for (int i = lane; i < kLongBufBytes / 8; i += 64) buf[i] = make_float2(0.0f, 0.0f);
   const int L = p.win_len;
   const float win_len_f = static_cast<float>(L);
-  const int left_lane_bytes = ((lane + 63) & 63) * 4;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kPairWaves;
-  int64_t g = static_cast<int64_t>(blockIdx.x) * kPairWaves + wid;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kLongWaves;
+  int64_t g = static_cast<int64_t>(blockIdx.x) * kLongWaves + wid;
   const int64_t last_pair = b.n_pairs - 1;
   auto rec_of = [&](int64_t pi) -> const PairRec* { return b.pair_tab + (pi < last_pair ? pi : last_pair); };
   // Sample ingest: a frame's samples come in as 16-byte pieces, lane l fetching pieces l and l + 64 (two wave
@@ -136,16 +118,10 @@ __global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
     int lane_v = lane;
     asm volatile("" : "+v"(lane_v));
     const int njl = (L - lane_v + 63) >> 6;
-    const int kq = lane_v >> 2, bq = lane_v & 3;     // pass C: (k1, quarter of b); pass D: (k1, c)
+    const Fft1024Maps maps = fft1024_maps(buf, lane_v);
     const float2* __restrict__ t_win = tab + kOffWin + lane_v * 18;
     const float2* __restrict__ t_tw1 = tab + kOffTw1 + lane_v * 18;
-    const float2* __restrict__ t_tw2 = tab + kOffTw2 + bq * 18;
-    const float2* __restrict__ base_lane = buf + lane_v;               // transpose 1 write, exchange write
-    float2* __restrict__ base_quad = buf + 68 * kq + bq;             // transpose 1 read, transpose 2 write
-    const float2* __restrict__ base_row = buf + 17 * lane_v;           // transpose 2 read
-    const float2* __restrict__ base_part =
-        buf + (kq == 0 ? ((4 - bq) & 3) : 4 * (16 - kq) + (3 - bq)) + (lane_v == 0 ? 64 : 0);  // partner lane
-    const int kappa = kq + 16 * bq;              // lane holds Z[kappa + 64 d] after pass D
+    const float2* __restrict__ t_tw2 = tab + kOffTw2 + maps.bq * 18;
 
     auto in_window = [&](int j) -> bool { return j < njl; };
     // the samples of this trip's two frames: registers -> LDS (whole pieces, then the tail)
@@ -234,7 +210,7 @@ __global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
       float rot[NJ];
       if (DITHER) {
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) rot[j] = from_left_lane(x[j] + neg_mean, left_lane_bytes);
+        for (int j = 0; j < NJ; ++j) rot[j] = from_left_lane(x[j] + neg_mean);
       }
       float e_post = 0.0f;
 #pragma unroll
@@ -284,55 +260,11 @@ __global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
       for (int j = 0; j < NJ; ++j) z[j] = make_float2(wa[j], two ? wb[j] : 0.0f);
 #pragma unroll
       for (int j = NJ; j < 16; ++j) z[j] = make_float2(0.0f, 0.0f);
-      // ---- B: pass 1 (FFT over j), twiddle W1024^(L k1), transpose ---------------------------------------
-      fft16_lf_head<NJ>(z);
-      float4 tw4[8];
-      read_quads_whole<8>(t_tw1, tw4);
-      lds_wait();
-#pragma unroll
-      for (int k1 = 1; k1 < 16; ++k1)
-        z[k1] = cmul(z[k1], (k1 & 1) ? make_float2(tw4[k1 >> 1].z, tw4[k1 >> 1].w)
-                                     : make_float2(tw4[k1 >> 1].x, tw4[k1 >> 1].y));
-#pragma unroll
-      for (int k1 = 0; k1 < 16; ++k1) const_cast<float2*>(base_lane)[k1 * 68] = z[k1];
-      wave_lds_sync();
-      // ---- C: lane (kq, bq): 4-point DFTs over the rows a for b = bq + 4 i, twiddle W64^(b c) -------------
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int a = 0; a < 4; ++a) z[4 * i + a] = base_quad[16 * a + 4 * i];
-      float4 tw2q[8];
-      read_quads_whole<8>(t_tw2, tw2q);
-      lds_wait();
-      wave_lds_sync();
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float2 o0, o1, o2, o3;
-        dft4(z[4 * i], z[4 * i + 1], z[4 * i + 2], z[4 * i + 3], o0, o1, o2, o3);
-        z[4 * i] = o0;
-        z[4 * i + 1] = cmul(o1, make_float2(tw2q[2 * i].z, tw2q[2 * i].w));
-        z[4 * i + 2] = cmul(o2, make_float2(tw2q[2 * i + 1].x, tw2q[2 * i + 1].y));
-        z[4 * i + 3] = cmul(o3, make_float2(tw2q[2 * i + 1].z, tw2q[2 * i + 1].w));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) base_quad[17 * c + 4 * i] = z[4 * i + c];
-      wave_lds_sync();
-      read16_b64(base_row, z);
-      lds_wait();
-      wave_lds_sync();
-      // ---- D: pass 3 (FFT over b): z[d] = Z[kappa + 64 d] -------------------------------------------------
-      fft16_lf(z);
-      __builtin_amdgcn_sched_barrier(0);
-      // ---- E: the two spectra.  Partner of k = kappa + 64 d (d < 8) is 1024 - k: register 15 - d of the lane
-      // with kappa' = 64 - kappa (own register 16 - d for kappa = 0) ---------------------------------------
-#pragma unroll
-      for (int d = 8; d < 16; ++d) const_cast<float2*>(base_lane)[(d - 8) * 64] = z[d];
-      wave_lds_sync();
+      // ---- B - D: the 1024-point complex transform, z[d] = Z[kappa + 64 d] ------------------------------------
+      cfft1024_passes<NJ>(z, t_tw1, t_tw2, maps);
+      // ---- E: the two spectra.  Partner of k = kappa + 64 d (d < 8) is 1024 - k ---------------------------------
       float2 zpart[8];
-#pragma unroll
-      for (int d = 0; d < 8; ++d) zpart[d] = base_part[(7 - d) * 64];
+      cfft1024_partner_reads(z, maps, zpart);
       lds_wait();
       wave_lds_sync();
       float pa[8], pb[8];
@@ -350,12 +282,12 @@ __global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
       }
       // self-paired bin 512 (lane 0, register 8): X_a[512] = Re Z[512], X_b[512] = Im Z[512]
       const float pa512 = z[8].x * z[8].x, pb512 = z[8].y * z[8].y;
-      float* __restrict__ ps_a = ps + kappa;
+      float* __restrict__ ps_a = ps + maps.kappa;
 #pragma unroll
       for (int d = 0; d < 8; ++d) ps_a[64 * d] = pa[d];
       if (lane == 0) ps_a[512] = pa512;
       if (two) {
-        float* __restrict__ ps_b = ps + kSpecB + kappa;
+        float* __restrict__ ps_b = ps + kSpecB + maps.kappa;
 #pragma unroll
         for (int d = 0; d < 8; ++d) ps_b[64 * d] = pb[d];
         if (lane == 0) ps_b[512] = pb512;
@@ -394,18 +326,8 @@ __global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
     // ---- F: epilogue (same conventions as mel_features_generic_kernel).  The two frames of a pair belong to one
     // utterance - one warp factor, one set of filters: the weights are fetched once per round for both -----------
     float log_energy[2] = {0.0f, 0.0f};
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-      if (f == 1 && !two) break;
-      if (KIND == SNF_KIND_PLP) {
-        // shennong's PLP floors with float64 eps and takes a double log (reference plp.py:191-193)
-        if ((p.need_raw || p.need_post) && lane == 0)
-          energy_out[g_a + f] = static_cast<double>(e_lin[f]);  // (plp_tail_kernel takes the double log)
-      } else if (p.need_raw || p.need_post) {
-        log_energy[f] = fast_log(floor_eps(e_lin[f]));
-        if (p.has_floor && log_energy[f] < p.log_energy_floor) log_energy[f] = p.log_energy_floor;
-      }
-    }
+    log_energy[0] = frame_log_energy<KIND>(p, lane, e_lin[0], g_a, energy_out);
+    if (two) log_energy[1] = frame_log_energy<KIND>(p, lane, e_lin[1], g_a + 1, energy_out);
     float* __restrict__ row_a = out + g_a * static_cast<int64_t>(out_cols);
     float* __restrict__ row_b = row_a + out_cols;
     if (KIND == SNF_KIND_SPECTROGRAM) {
@@ -519,53 +441,9 @@ __global__ __launch_bounds__(kPairWaves * 64) void fbank1024x2_kernel(
       }
       if (KIND == SNF_KIND_MFCC) {
         wave_lds_sync();
-        // DCT-II: teams of 4 lanes per cepstral coefficient, 16 coefficients per round, both frames
-        const int ct = lane >> 2, cl = lane & 3;
-        for (int c0 = 0; c0 < p.num_ceps; c0 += 16) {
-          const int c = c0 + ct;
-          const bool ca = c < p.num_ceps;
-          const float* __restrict__ dm = p.dct + (ca ? c : 0) * nb;
-          float va = 0.0f, vb = 0.0f;
-          for (int m0 = 0; m0 < nb; m0 += 32) {  // 8 coefficients per lane in flight
-            float dv[8], mva[8], mvb[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const int m = m0 + cl + 4 * e;
-              dv[e] = dm[m < nb ? m : 0];
-              mva[e] = melbuf[m < nb ? m : 0];
-              mvb[e] = melbuf[128 + (m < nb ? m : 0)];
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              va += (m0 + cl + 4 * e < nb) ? dv[e] * mva[e] : 0.0f;
-              vb += (m0 + cl + 4 * e < nb) ? dv[e] * mvb[e] : 0.0f;
-            }
-          }
-          va += dpp_row_ror<0xB1>(va);
-          vb += dpp_row_ror<0xB1>(vb);
-          va += dpp_row_ror<0x4E>(va);
-          vb += dpp_row_ror<0x4E>(vb);
-          if (ca && cl == 0) {
-            if (p.lifter) {
-              va *= p.lifter[c];
-              vb *= p.lifter[c];
-            }
-            if (c == 0 && p.use_energy) {
-              va = log_energy[0];
-              vb = log_energy[1];
-            }
-            int oc = c;
-            if (p.htk_compat) {
-              oc = c == 0 ? p.num_ceps - 1 : c - 1;
-              if (c == 0 && !p.use_energy) {
-                va = static_cast<float>(static_cast<double>(va) * 1.4142135623730950488016887);
-                vb = static_cast<float>(static_cast<double>(vb) * 1.4142135623730950488016887);
-              }
-            }
-            row_a[oc] = va;
-            if (two) row_b[oc] = vb;
-          }
-        }
+        const float* const mel[2] = {melbuf, melbuf + 128};
+        float* const rows[2] = {row_a, row_b};
+        mfcc_dct_tail<2>(p, lane, two, mel, log_energy, rows);
       }
     }
     wave_lds_sync();  // the next trip reuses the buffer
@@ -590,75 +468,43 @@ bool fbank1024x2_eligible(const MelParams& mp) {
 
 // Window values and twiddles of the kernel, laid out per lane (float2 units, see kOff*)
 void fbank1024x2_tables(const MelParams& mp, const std::vector<float>& window, std::vector<float>* blob) {
-  constexpr double kTwoPi = 6.283185307179586476925286766559005;
   blob->assign(static_cast<size_t>(kPairTableFloat2) * 2, 0.0f);
   float* t = blob->data();
-  auto put = [&](int index, double re, double im) {
-    t[2 * index] = static_cast<float>(re);
-    t[2 * index + 1] = static_cast<float>(im);
-  };
-  for (int lane = 0; lane < 64; ++lane) {
+  fft1024_twiddle_tables(t, kOffTw1, kOffTw2);
+  for (int lane = 0; lane < 64; ++lane)
     for (int j = 0; j < 16; ++j) {
       const int n = lane + 64 * j;
-      const double w = n < mp.win_len ? window[n] : 0.0;
-      put(kOffWin + lane * 18 + j, w, w);
-      const double a1 = -kTwoPi * ((lane * j) % 1024) / 1024.0;  // W1024^(lane k1), k1 = j
-      put(kOffTw1 + lane * 18 + j, std::cos(a1), std::sin(a1));
+      t[2 * (kOffWin + lane * 18 + j)] = t[2 * (kOffWin + lane * 18 + j) + 1] =
+          n < mp.win_len ? window[n] : 0.0f;
     }
-  }
-  for (int bq = 0; bq < 4; ++bq)
-    for (int i = 0; i < 4; ++i)
-      for (int c = 0; c < 4; ++c) {
-        const double a = -kTwoPi * (((bq + 4 * i) * c) % 64) / 64.0;
-        put(kOffTw2 + bq * 18 + i * 4 + c, std::cos(a), std::sin(a));
-      }
 }
 
 int launch_fbank1024x2(const MelParams& p, const BatchArgs& b, const float* tables, float* out, int out_cols,
                        double* energy_out, hipStream_t stream) {
   if (b.n_pairs <= 0) return SNF_OK;
-  const int lds = kPairTableBytes + kPairWaves * kPairBufBytes;
-  int64_t blocks = (b.n_pairs + kPairWaves - 1) / kPairWaves;
+  const int lds = kPairTableBytes + kLongWaves * kLongBufBytes;
+  int64_t blocks = (b.n_pairs + kLongWaves - 1) / kLongWaves;
   if (blocks > 256) blocks = 256;  // one persistent workgroup per CU, grid-stride over the pairs
   const int rows = (p.win_len + 63) / 64;
   static const float split_ratio = [] {
     const char* e = getenv("SNF_PAIR_SPLIT_RATIO");   // (experiments: 0 splits every pair, inf none)
     return e ? static_cast<float>(atof(e)) : kSplitRatio;
   }();
-#define SNF_PAIR4(NJ_, KIND_, DI_, SN_)                                                                          \
-  do {                                                                                                           \
-    SNF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fbank1024x2_kernel<NJ_, KIND_, DI_, SN_>),  \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));                        \
-    hipLaunchKernelGGL((fbank1024x2_kernel<NJ_, KIND_, DI_, SN_>), dim3(static_cast<unsigned>(blocks)),         \
-                       dim3(kPairWaves * 64), lds, stream, p, b, reinterpret_cast<const float2*>(tables),        \
-                       split_ratio, out, out_cols, energy_out);                                                  \
-  } while (0)
-#define SNF_PAIR3(NJ_, KIND_, DI_)                                                                        \
-  do {                                                                                                    \
-    if (p.snip_edges) SNF_PAIR4(NJ_, KIND_, DI_, true);                                                   \
-    else SNF_PAIR4(NJ_, KIND_, DI_, false);                                                               \
-  } while (0)
-#define SNF_PAIR2(NJ_, KIND_)                                                                             \
-  do {                                                                                                    \
-    if (p.dither != 0.0f) SNF_PAIR3(NJ_, KIND_, true);                                                    \
-    else SNF_PAIR3(NJ_, KIND_, false);                                                                    \
-  } while (0)
-#define SNF_PAIR(NJ_)                                                                                     \
-  do {                                                                                                    \
-    if (p.kind == SNF_KIND_FBANK) SNF_PAIR2(NJ_, SNF_KIND_FBANK);                                         \
-    else if (p.kind == SNF_KIND_MFCC) SNF_PAIR2(NJ_, SNF_KIND_MFCC);                                      \
-    else if (p.kind == SNF_KIND_PLP) SNF_PAIR2(NJ_, SNF_KIND_PLP);                                        \
-    else SNF_PAIR2(NJ_, SNF_KIND_SPECTROGRAM);                                                            \
-  } while (0)
-  if (rows <= 9) SNF_PAIR(9);
-  else if (rows <= 13) SNF_PAIR(13);
-  else SNF_PAIR(16);
-#undef SNF_PAIR2
-#undef SNF_PAIR3
-#undef SNF_PAIR4
-#undef SNF_PAIR
-  SNF_HIP_CHECK(hipGetLastError());
-  return SNF_OK;
+  auto launch = [&](auto nj) {
+    return with_kind_dither_snip(p, [&](auto kind, auto dither, auto snip) {
+      const auto kernel = fbank1024x2_kernel<decltype(nj)::value, decltype(kind)::value, decltype(dither)::value,
+                                             decltype(snip)::value>;
+      SNF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLongWaves * 64), lds, stream, p, b,
+                         reinterpret_cast<const float2*>(tables), split_ratio, out, out_cols, energy_out);
+      SNF_HIP_CHECK(hipGetLastError());
+      return static_cast<int>(SNF_OK);
+    });
+  };
+  if (rows <= 9) return launch(std::integral_constant<int, 9>{});
+  if (rows <= 13) return launch(std::integral_constant<int, 13>{});
+  return launch(std::integral_constant<int, 16>{});
 }
 
 }  // namespace snf

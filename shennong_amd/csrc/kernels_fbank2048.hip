@@ -1,6 +1,7 @@
 // Register-resident spectrogram / filterbank / MFCC / PLP-mel kernel for frames that pad to 2048 samples
 // (25 ms windows at 44.1 and 48 kHz: the reference tests MFCC at 44.1 kHz, test/processor/test_mfcc.py:
-// 129-137) and, zero-extended, to 1024 samples (32 kHz), on gfx950.  Same per-frame recipe as
+// 129-137), on gfx950; frames that pad to 1024 samples run two at a time on the same transform
+// (kernels_fbank1024x2.hip).  Same per-frame recipe as
 // kernels_mel.hip ([KALDI-UPSTREAM] feature-window.cc ProcessWindow order, feature-fbank.cc,
 // feature-mfcc.cc, MelBanks::Compute; reached by the reference at shennong/processor/base.py:429-431),
 // with the LDS radix-4 FFT of that kernel replaced by register passes:
@@ -10,6 +11,7 @@
 //      + immediate; the next frame's samples are requested when this frame's transform is done and land
 //      during its mel phase); DC removal over the wave, pre-emphasis (left neighbour through 16
 //      ds_bpermute issued together), window
+//   B-D the 1024-point complex transform, shared with kernels_fbank1024x2.hip (cfft1024_passes, device_fft1024.h):
 //   B  16-point FFT over j in registers, twiddle W1024^(L k1), transpose through the wave's 8.5 KB LDS
 //      buffer (row pitches 68 and 17 complex: every access is bank-conflict free AND a lane-constant base
 //      plus an immediate offset - six address registers serve all ~140 LDS accesses of a frame)
@@ -21,11 +23,10 @@
 //      taps of every 32-tap slice of the filter (16-byte weight loads from a per-plan table - one per warp
 //      factor for VTLN - in which the filters start at multiples of 4 bins, are zero-padded to whole
 //      slices and rotated by the team index: no per-tap test, conflict-free LDS reads); DCT-II by teams
-//      of 4 lanes per coefficient; log / lifter / energy conventions as in the generic kernel
+//      of 4 lanes per coefficient (mfcc_dct_tail, device_fft1024.h); log / lifter / energy conventions as in
+//      the generic kernel
 // The index maps were checked lane by lane against numpy.fft, and every LDS access against the bank model
 // of MI355X_MICROARCH.md, before the first GPU run (tools/model_fbank2048.py, tests/test_fbank2048_model.py).
-// Frames that pad to 1024 samples run as the 2048-point transform of the zero-extended frame:
-// X2048[2 k] = X1024[k]; their spectrum (the even bins) is kept compactly.
 #include <float.h>
 
 #include <cmath>
@@ -35,39 +36,17 @@
 
 #include "snf_internal.h"
 #include "device_fft.h"
+#include "device_fft1024.h"
 
 namespace snf {
 
 namespace {
 
-constexpr int kLongWaves = 16;                 // one workgroup per CU: 16 frames in flight
-constexpr int kLongBufBytes = 1088 * 8;        // wave-private LDS: 16 rows x (64 + 4) complex = 64 rows x 17
 // table blob (float2 units): window pairs [64][18] | W1024^(L k1) [64][18] | W2048^(kappa + 64 d) [64][10]
-// | W64^(b c) [4][16 + 2]; rows padded so that ds_read_b128 is conflict-free (the four rows of the last table
-// are broadcast to 16 lanes each: 128-byte rows would put all four on the same banks)
+// | W64^(b c) [4][16 + 2]; rows padded so that ds_read_b128 is conflict-free (fft1024_twiddle_tables)
 constexpr int kOffWin = 0, kOffTw1 = 64 * 18, kOffTwU = 2 * 64 * 18, kOffTw2 = 2 * 64 * 18 + 64 * 10;
 constexpr int kLongTableFloat2 = kOffTw2 + 4 * 18;
 constexpr int kLongTableBytes = kLongTableFloat2 * 8;
-
-__device__ __forceinline__ float readlane_f(float v, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-// sum over the 64 lanes, the same value in every lane
-__device__ __forceinline__ float wave_sum64(float v) {
-  v = row_sum16(v);
-  return (readlane_f(v, 0) + readlane_f(v, 16)) + (readlane_f(v, 32) + readlane_f(v, 48));
-}
-// a wave-uniform 64-bit value as a scalar (keeps the base of the sample loads in SGPRs)
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane(static_cast<int>(v));
-  const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<int>(v >> 32));
-  return static_cast<int64_t>((static_cast<unsigned long long>(hi) << 32) | lo);
-}
-// value of `v` in lane (lane - 1) mod 64: a DPP move with wave_ror:1 (gfx9 keeps the whole-wave rotations;
-// checked on the device with tools/ubench_wave_ror.hip), not a trip through the LDS crossbar (ds_bpermute)
-__device__ __forceinline__ float from_left_lane(float v, int) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x13C, 0xf, 0xf, false));
-}
 
 }  // namespace
 
@@ -76,7 +55,7 @@ __device__ __forceinline__ float from_left_lane(float v, int) {
 // (the epilogue of one kind per instantiation keeps the scalar register file free of the others' flags)
 template <int NJ, int KIND, bool DITHER, bool SNIP>
 __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
-    const MelParams p, const BatchArgs b, const float2* __restrict__ gtab, const int bin_step,
+    const MelParams p, const BatchArgs b, const float2* __restrict__ gtab,
     float* __restrict__ out, const int out_cols, double* __restrict__ energy_out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float2* tab = reinterpret_cast<float2*>(smem);
@@ -92,7 +71,6 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
   for (int i = lane; i < kLongBufBytes / 8; i += 64) buf[i] = make_float2(0.0f, 0.0f);
   const int L = p.win_len;
   const float win_len_f = static_cast<float>(L);
-  const int left_lane_bytes = ((lane + 63) & 63) * 4;
   typedef int __attribute__((aligned(2))) int_a2;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kLongWaves;
   int64_t g = static_cast<int64_t>(blockIdx.x) * kLongWaves + wid;
@@ -136,18 +114,12 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
     int lane_v = lane;
     asm volatile("" : "+v"(lane_v));
     const int njl = (L / 2 - lane_v + 63) >> 6;
-    const int kq = lane_v >> 2, bq = lane_v & 3;     // pass C: (k1, quarter of b); pass D: (k1, c)
+    const Fft1024Maps maps = fft1024_maps(buf, lane_v);
     const float2* __restrict__ t_win = tab + kOffWin + lane_v * 18;
     const float2* __restrict__ t_tw1 = tab + kOffTw1 + lane_v * 18;
     const float2* __restrict__ t_twu = tab + kOffTwU + lane_v * 10;
-    const float2* __restrict__ t_tw2 = tab + kOffTw2 + bq * 18;
-    // lane-constant LDS bases (float2 index into the wave's buffer); every access adds a compile-time offset
-    const float2* __restrict__ base_lane = buf + lane_v;               // transpose 1 write, exchange write
-    float2* __restrict__ base_quad = buf + 68 * kq + bq;             // transpose 1 read, transpose 2 write
-    const float2* __restrict__ base_row = buf + 17 * lane_v;           // transpose 2 read
-    const float2* __restrict__ base_part =
-        buf + (kq == 0 ? ((4 - bq) & 3) : 4 * (16 - kq) + (3 - bq)) + (lane_v == 0 ? 64 : 0);  // partner lane
-    const int kappa = kq + 16 * bq;              // lane holds Z[kappa + 64 d] after pass D
+    const float2* __restrict__ t_tw2 = tab + kOffTw2 + maps.bq * 18;
+    const int kappa = maps.kappa;                // lane holds Z[kappa + 64 d] after pass D
     float* __restrict__ ps_lo = ps + kappa;      // P[kappa + 64 d]
     float* __restrict__ ps_hi = ps + (576 - kappa);  // P[1024 - kappa - 64 d] = ps_hi[448 - 64 d]
 
@@ -180,7 +152,7 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         if (in_window(j)) {
-          const float2 v = base_lane[64 * j];
+          const float2 v = maps.base_lane[64 * j];
           xe[j] = v.x;
           xo[j] = v.y;
         }
@@ -218,7 +190,7 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
     // (same j), lane 63 of j-1 for lane 0.  All 16 exchanges are issued before the first one is used.
     float rot[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) rot[j] = from_left_lane(xo[j] + neg_mean, left_lane_bytes);
+    for (int j = 0; j < NJ; ++j) rot[j] = from_left_lane(xo[j] + neg_mean);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {  // (window weights in two halves: 16 live registers instead of 32)
       if (8 * h < NJ) {
@@ -249,57 +221,12 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
     }
     __builtin_amdgcn_sched_barrier(0);
 
-    // ---- B: pass 1 (FFT over j), twiddle W1024^(L k1), transpose ---------------------------------------
-    // (rows j >= NJ are the zero padding: the first layer skips them; butterflies with folded twiddles)
-    fft16_lf_head<NJ>(z);
-    float4 tw4[8];
-    read_quads_whole<8>(t_tw1, tw4);
-    lds_wait();
-#pragma unroll
-    for (int k1 = 1; k1 < 16; ++k1)
-      z[k1] = cmul(z[k1], (k1 & 1) ? make_float2(tw4[k1 >> 1].z, tw4[k1 >> 1].w)
-                                   : make_float2(tw4[k1 >> 1].x, tw4[k1 >> 1].y));
-#pragma unroll
-    for (int k1 = 0; k1 < 16; ++k1) const_cast<float2*>(base_lane)[k1 * 68] = z[k1];
-    wave_lds_sync();
-    // ---- C: lane (kq, bq): 4-point DFTs over the rows a for b = bq + 4 i, twiddle W64^(b c) --------------
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int a = 0; a < 4; ++a) z[4 * i + a] = base_quad[16 * a + 4 * i];
-    float4 tw2q[8];
-    read_quads_whole<8>(t_tw2, tw2q);
-    lds_wait();
-    wave_lds_sync();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float2 o0, o1, o2, o3;
-      dft4(z[4 * i], z[4 * i + 1], z[4 * i + 2], z[4 * i + 3], o0, o1, o2, o3);
-      z[4 * i] = o0;
-      z[4 * i + 1] = cmul(o1, make_float2(tw2q[2 * i].z, tw2q[2 * i].w));
-      z[4 * i + 2] = cmul(o2, make_float2(tw2q[2 * i + 1].x, tw2q[2 * i + 1].y));
-      z[4 * i + 3] = cmul(o3, make_float2(tw2q[2 * i + 1].z, tw2q[2 * i + 1].w));
-    }
-    // transpose: row r = 4 kq + c (pitch 17) holds b = 0..15
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) base_quad[17 * c + 4 * i] = z[4 * i + c];
-    wave_lds_sync();
-    read16_b64(base_row, z);
-    lds_wait();
-    wave_lds_sync();
-    // ---- D: pass 3 (FFT over b): z[d] = Z[kappa + 64 d] ---------------------------------------------------
-    fft16_lf(z);
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- E: real-FFT unpack + power.  Partner of k = kappa + 64 d (d < 8) is 1024 - k: register 15 - d of
-    // the lane with kappa' = 64 - kappa (own register 16 - d for kappa = 0) ---------------------------------
-#pragma unroll
-    for (int d = 8; d < 16; ++d) const_cast<float2*>(base_lane)[(d - 8) * 64] = z[d];
-    wave_lds_sync();
+    // ---- B - D: the 1024-point complex transform, z[d] = Z[kappa + 64 d] --------------------------------------
+    cfft1024_passes<NJ>(z, t_tw1, t_tw2, maps);
+    // ---- E: real-FFT unpack + power.  Partner of k = kappa + 64 d (d < 8) is 1024 - k; the unpack twiddles
+    // come in inside the same wait ------------------------------------------------------------------------------
     float2 zpart[8];
-#pragma unroll
-    for (int d = 0; d < 8; ++d) zpart[d] = base_part[(7 - d) * 64];
+    cfft1024_partner_reads(z, maps, zpart);
     float4 twuq[4];
     read_quads_whole<4>(t_twu, twuq);
     lds_wait();
@@ -324,26 +251,12 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
       pm[0] = ny * ny;
     }
     const float p512 = z[8].x * z[8].x + z[8].y * z[8].y;  // self-paired bin 512: lane 0, register 8
-    if (bin_step == 1) {
 #pragma unroll
-      for (int d = 0; d < 8; ++d) {
-        ps_lo[64 * d] = pk[d];
-        ps_hi[448 - 64 * d] = pm[d];
-      }
-      if (lane == 0) ps[512] = p512;
-    } else {
-      // zero-extended 1024-sample frame: its spectrum is the even bins, kept compactly (bin k at k / 2)
-      if ((kappa & 1) == 0) {
-        float* __restrict__ pe_lo = ps + (kappa >> 1);
-        float* __restrict__ pe_hi = ps + (288 - (kappa >> 1));  // (1024 - kappa - 64 d) / 2 = pe_hi[224 - 32 d]
-#pragma unroll
-        for (int d = 0; d < 8; ++d) {
-          pe_lo[32 * d] = pk[d];
-          pe_hi[224 - 32 * d] = pm[d];
-        }
-      }
-      if (lane == 0) ps[256] = p512;
+    for (int d = 0; d < 8; ++d) {
+      ps_lo[64 * d] = pk[d];
+      ps_hi[448 - 64 * d] = pm[d];
     }
+    if (lane == 0) ps[512] = p512;
     wave_lds_sync();
     if (KIND == SNF_KIND_FBANK && !p.use_power) {  // magnitude spectrum
       for (int k = lane; k <= p.half; k += 64) ps[k] = sqrtf(ps[k]);
@@ -359,15 +272,7 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
     }
     start_next = b.frame_start[clamp_frame(g + 2 * stride)];
     // ---- F: epilogue (same conventions as mel_features_generic_kernel) -----------------------------------
-    float log_energy = 0.0f;
-    if (KIND == SNF_KIND_PLP) {
-      // shennong's PLP floors with float64 eps and takes a double log (reference plp.py:191-193)
-      if ((p.need_raw || p.need_post) && lane == 0)
-        energy_out[g] = static_cast<double>(e_lin);  // (plp_tail_kernel takes the double log)
-    } else if (p.need_raw || p.need_post) {
-      log_energy = fast_log(floor_eps(e_lin));
-      if (p.has_floor && log_energy < p.log_energy_floor) log_energy = p.log_energy_floor;
-    }
+    const float log_energy = frame_log_energy<KIND>(p, lane, e_lin, g, energy_out);
     float* __restrict__ row = out + g * static_cast<int64_t>(out_cols);
     if (KIND == SNF_KIND_SPECTROGRAM) {
       for (int k = lane; k <= p.half; k += 64) {
@@ -442,38 +347,9 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
         row[p.htk_compat ? nb : 0] = log_energy;
       if (KIND == SNF_KIND_MFCC) {
         wave_lds_sync();
-        // DCT-II: teams of 4 lanes per cepstral coefficient, 16 coefficients per round
-        const int ct = lane >> 2, cl = lane & 3;
-        for (int c0 = 0; c0 < p.num_ceps; c0 += 16) {
-          const int c = c0 + ct;
-          const bool ca = c < p.num_ceps;
-          const float* __restrict__ dm = p.dct + (ca ? c : 0) * nb;
-          float v = 0.0f;
-          for (int m0 = 0; m0 < nb; m0 += 32) {  // 8 coefficients per lane in flight
-            float dv[8], mv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const int m = m0 + cl + 4 * e;
-              dv[e] = dm[m < nb ? m : 0];
-              mv[e] = melbuf[m < nb ? m : 0];
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v += (m0 + cl + 4 * e < nb) ? dv[e] * mv[e] : 0.0f;
-          }
-          v += dpp_row_ror<0xB1>(v);
-          v += dpp_row_ror<0x4E>(v);
-          if (ca && cl == 0) {
-            if (p.lifter) v *= p.lifter[c];
-            if (c == 0 && p.use_energy) v = log_energy;
-            int oc = c;
-            if (p.htk_compat) {
-              oc = c == 0 ? p.num_ceps - 1 : c - 1;
-              if (c == 0 && !p.use_energy)
-                v = static_cast<float>(static_cast<double>(v) * 1.4142135623730950488016887);
-            }
-            row[oc] = v;
-          }
-        }
+        const float* const mel[1] = {melbuf};
+        float* const rows[1] = {row};
+        mfcc_dct_tail<1>(p, lane, false, mel, &log_energy, rows);
       }
     }
     wave_lds_sync();  // the next frame reuses the buffer
@@ -485,7 +361,7 @@ __global__ __launch_bounds__(kLongWaves * 64) void fbank2048_kernel(
 // ---------------------------------------------------------------------------------------------------
 bool fbank2048_eligible(const MelParams& mp) {
   if (getenv("SNF_DISABLE_FAST2048")) return false;
-  if (!mp.pow2 || (mp.padded != 2048 && mp.padded != 1024)) return false;
+  if (!mp.pow2 || mp.padded != 2048) return false;
   if (mp.win_len & 1) return false;
   if (mp.kind != SNF_KIND_FBANK && mp.kind != SNF_KIND_MFCC && mp.kind != SNF_KIND_PLP &&
       mp.kind != SNF_KIND_SPECTROGRAM)
@@ -503,27 +379,20 @@ void fbank2048_tables(const MelParams& mp, const std::vector<float>& window, std
     t[2 * index] = static_cast<float>(re);
     t[2 * index + 1] = static_cast<float>(im);
   };
+  fft1024_twiddle_tables(t, kOffTw1, kOffTw2);
   for (int lane = 0; lane < 64; ++lane) {
     for (int j = 0; j < 16; ++j) {
       const int n = lane + 64 * j;
       const double w0 = 2 * n < mp.win_len ? window[2 * n] : 0.0;
       const double w1 = 2 * n + 1 < mp.win_len ? window[2 * n + 1] : 0.0;
       put(kOffWin + lane * 18 + j, w0, w1);
-      const double a1 = -kTwoPi * ((lane * j) % 1024) / 1024.0;  // W1024^(lane k1), k1 = j
-      put(kOffTw1 + lane * 18 + j, std::cos(a1), std::sin(a1));
     }
     const int kappa = (lane >> 2) + 16 * (lane & 3);
     for (int d = 0; d < 8; ++d) {
-      const double a = -kTwoPi * (kappa + 64 * d) / 2048.0;
+      const double a = -kTwoPi * (kappa + 64 * d) / 2048.0;  // the real-FFT unpack: W2048^(kappa + 64 d)
       put(kOffTwU + lane * 10 + d, std::cos(a), std::sin(a));
     }
   }
-  for (int bq = 0; bq < 4; ++bq)
-    for (int i = 0; i < 4; ++i)
-      for (int c = 0; c < 4; ++c) {
-        const double a = -kTwoPi * (((bq + 4 * i) * c) % 64) / 64.0;
-        put(kOffTw2 + bq * 18 + i * 4 + c, std::cos(a), std::sin(a));
-      }
 }
 
 int launch_fbank2048(const MelParams& p, const BatchArgs& b, const float* tables, float* out, int out_cols,
@@ -533,40 +402,21 @@ int launch_fbank2048(const MelParams& p, const BatchArgs& b, const float* tables
   int64_t blocks = (b.total_frames + kLongWaves - 1) / kLongWaves;
   if (blocks > 256) blocks = 256;  // one persistent workgroup per CU, grid-stride over the frames
   const int rows = (p.win_len + 127) / 128;
-#define SNF_LONG4(NJ_, KIND_, DI_, SN_)                                                                             \
-  do {                                                                                                    \
-    SNF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fbank2048_kernel<NJ_, KIND_, DI_, SN_>),       \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds));                 \
-    hipLaunchKernelGGL((fbank2048_kernel<NJ_, KIND_, DI_, SN_>), dim3(static_cast<unsigned>(blocks)),               \
-                       dim3(kLongWaves * 64), lds, stream, p, b, reinterpret_cast<const float2*>(tables), \
-                       2048 / p.padded, out, out_cols, energy_out);                                       \
-  } while (0)
-#define SNF_LONG3(NJ_, KIND_, DI_)                                                                         \
-  do {                                                                                                    \
-    if (p.snip_edges) SNF_LONG4(NJ_, KIND_, DI_, true);                                                   \
-    else SNF_LONG4(NJ_, KIND_, DI_, false);                                                               \
-  } while (0)
-#define SNF_LONG2(NJ_, KIND_)                                                                              \
-  do {                                                                                                    \
-    if (p.dither != 0.0f) SNF_LONG3(NJ_, KIND_, true);                                                    \
-    else SNF_LONG3(NJ_, KIND_, false);                                                                    \
-  } while (0)
-#define SNF_LONG(NJ_)                                                                                      \
-  do {                                                                                                    \
-    if (p.kind == SNF_KIND_FBANK) SNF_LONG2(NJ_, SNF_KIND_FBANK);                                         \
-    else if (p.kind == SNF_KIND_MFCC) SNF_LONG2(NJ_, SNF_KIND_MFCC);                                      \
-    else if (p.kind == SNF_KIND_PLP) SNF_LONG2(NJ_, SNF_KIND_PLP);                                        \
-    else SNF_LONG2(NJ_, SNF_KIND_SPECTROGRAM);                                                            \
-  } while (0)
-  if (rows <= 9) SNF_LONG(9);
-  else if (rows <= 10) SNF_LONG(10);
-  else SNF_LONG(16);
-#undef SNF_LONG2
-#undef SNF_LONG3
-#undef SNF_LONG4
-#undef SNF_LONG
-  SNF_HIP_CHECK(hipGetLastError());
-  return SNF_OK;
+  auto launch = [&](auto nj) {
+    return with_kind_dither_snip(p, [&](auto kind, auto dither, auto snip) {
+      const auto kernel = fbank2048_kernel<decltype(nj)::value, decltype(kind)::value, decltype(dither)::value,
+                                           decltype(snip)::value>;
+      SNF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(kLongWaves * 64), lds, stream, p, b,
+                         reinterpret_cast<const float2*>(tables), out, out_cols, energy_out);
+      SNF_HIP_CHECK(hipGetLastError());
+      return static_cast<int>(SNF_OK);
+    });
+  };
+  if (rows <= 9) return launch(std::integral_constant<int, 9>{});
+  if (rows <= 10) return launch(std::integral_constant<int, 10>{});
+  return launch(std::integral_constant<int, 16>{});
 }
 
 }  // namespace snf

@@ -266,7 +266,7 @@ bool fbank512b_shape_ok(const Fast512Params& p, bool per_utt);
 int launch_fbank512b(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
                      double* energy_out, hipStream_t stream);
 
-// ---- register-resident 2048-point path (kernels_fbank2048.hip): 44.1 / 48 kHz frames, 32 kHz zero-extended
+// ---- register-resident 2048-point path (kernels_fbank2048.hip): frames that pad to 2048 samples (44.1 / 48 kHz)
 bool fbank2048_eligible(const MelParams& mp);
 void fbank2048_tables(const MelParams& mp, const std::vector<float>& window, std::vector<float>* blob);
 int launch_fbank2048(const MelParams& p, const BatchArgs& b, const float* tables, float* out, int out_cols,

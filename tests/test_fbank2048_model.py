@@ -1,7 +1,8 @@
-"""CPU check of the design of fbank2048_kernel: the lane / register / LDS index maps of its three register
-passes, two transposes and partner exchange reproduce numpy's FFT and power spectrum, and every LDS access
-of the transform is bank-conflict free under the bank model of MI355X_MICROARCH.md (the 2-way conflicts of
-the 17 power-spectrum writes are the known exception)."""
+"""CPU check of the design of the 1024-point complex transform shared by fbank2048_kernel and
+fbank1024x2_kernel (device_fft1024.h): the lane / register / LDS index maps of its three register passes, two
+transposes and partner exchange reproduce numpy's FFT - and, with fbank2048_kernel's real-FFT unpack behind
+them, its power spectrum -, and every LDS access of the transform is bank-conflict free under the bank model
+of MI355X_MICROARCH.md (the 2-way conflicts of the 17 power-spectrum writes are the known exception)."""
 import os
 import re
 import subprocess

@@ -896,6 +896,28 @@ def test_fast_kernel_long_frames(gpu, cls, sample_rate, opts, snip_edges):
         assert_close(f.data, _oracle(proc, w, wf), rtol=1e-4, what=f'{proc.name} warp {wf} {opts}')
 
 
+@pytest.mark.parametrize('snip_edges', [True, False])
+@pytest.mark.parametrize('sample_rate, kernel', [(44100, 'fbank2048_kernel'), (32000, 'fbank1024x2_kernel')])
+@pytest.mark.parametrize('cls', [FilterbankProcessor, MfccProcessor, PlpProcessor, SpectrogramProcessor])
+def test_long_frames_dither_instantiations(gpu, cls, sample_rate, kernel, snip_edges):
+    """the DITHER = true instantiations of every kind of the long-frame kernels (test_dither_is_gaussian_long_frames
+    runs spectrograms only: a launch ladder that picked the wrong kind for a dithered plan would pass it).  The
+    dither is too small to survive the addition to a 16-bit sample (1e-12 against an ulp of 1.2e-7 at 1; a zero
+    sample becomes ~1e-12), so the features must match the dither-0 oracle at the suite's own tolerance.  Not
+    smaller than that: the generator squares the amplitude and multiplies it by a log2 down to 1.7e-7 (gauss_pair /
+    dither_scale in device_fft.h), which stays a normal float down to an amplitude of 2.3e-16 only"""
+    n = int(0.35 * sample_rate)
+    waves = [synth.utterances(21 + i, 1, n + 1013 * i, sample_rate)[0] for i in range(3)]
+    proc = cls(sample_rate=sample_rate, dither=1e-12, snip_edges=snip_edges)
+    clean = cls(sample_rate=sample_rate, dither=0, snip_edges=snip_edges)
+    feats = proc._process_batch([Audio(w, sample_rate) for w in waves])
+    assert _backend.get_plan(proc._build_options()).kernel_name(1) == kernel
+    for w, f in zip(waves, feats):
+        want = _oracle(clean, w)
+        assert f.shape == want.shape
+        assert_close(f.data, want, rtol=1e-4, what=f'{cls.__name__} {sample_rate} dither 1e-12')
+
+
 @pytest.mark.parametrize('sample_rate', [32000, 22050, 8000])
 def test_paired_frames_of_unequal_energy(gpu, sample_rate):
     """two frames per transform share their roundings, the louder frame sets the error floor of both: a quiet

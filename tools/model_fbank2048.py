@@ -1,7 +1,10 @@
-"""Lane-level numpy model of the 2048-point real FFT data flow of fbank2048_kernel: lane / register / LDS
-index maps (row pitches 68 and 17), twiddles, partner exchange, checked against numpy.fft, and the LDS bank
-model of MI355X_MICROARCH.md applied to every access.  `python tools/model_fbank2048.py` prints the errors and
-any bank conflict; tests/test_fbank2048_model.py runs it on CPU."""
+"""Lane-level numpy model of the 1024-point complex transform that fbank2048_kernel and fbank1024x2_kernel share
+(cfft1024_passes / cfft1024_partner_reads in shennong_amd/csrc/device_fft1024.h): lane / register / LDS index
+maps (row pitches 68 and 17), twiddles, partner exchange, checked against numpy.fft, and the LDS bank model of
+MI355X_MICROARCH.md applied to every access.  Behind the shared part it follows fbank2048_kernel: the real-FFT
+unpack of one 2048-sample frame and its power-spectrum writes (fbank1024x2_kernel separates two frames there
+without a twiddle).  `python tools/model_fbank2048.py` prints the errors and any bank conflict;
+tests/test_fbank2048_model.py runs it on CPU."""
 import numpy as np
 rng = np.random.default_rng(0)
 x = rng.standard_normal(2048)
