@@ -469,6 +469,30 @@ int snf_bottleneck_nn_input(int device_id, const float* d_logmel, const uint8_t*
 int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
                            const int32_t* h_widths, const float* const* h_params, float* d_bn, float* d_out,
                            void* stream);
+/* bfloat16 matrix-core path for the layers that read sigmoid outputs in (0, 1).  The numerics contract: at
+ * the input of such a layer every activation and every weight is rounded to bfloat16 (round to nearest, ties
+ * to even; a NaN stays a NaN), the products are accumulated in float32 on the matrix cores
+ * (v_mfma_f32_32x32x16_bf16), bias and activation are float32, the output is float32.  An element depends on
+ * its own input row, its weight column and k only: not on m, nor on the row's place in the batch.
+ *
+ * Packed weights: the image of d_w[k x n] is Wt[n][kp] uint16 (bfloat16 bits), k-contiguous per output column,
+ * kp = k rounded up to a multiple of 64 and zero beyond k; it must be 16-byte aligned.
+ * snf_packed_weights_bf16_size returns its number of uint16 elements, n * kp (host only; 0 unless
+ * 1 <= k, n <= 2^20). */
+int64_t snf_packed_weights_bf16_size(int32_t k, int32_t n);
+/* d_packed = the packed bfloat16 image of d_w[k x n] row-major float32 (prepared once per network: replaces the
+ * reference's float64 `W` operands of bottleneck.py:485-500 for these layers). */
+int snf_pack_weights_bf16(int device_id, const float* d_w, int32_t k, int32_t n, uint16_t* d_packed, void* stream);
+/* d_y[m x n] = act(bf16(d_x[m x k]) bf16(W) + d_b[n]) with W given as its packed image; float32 d_x, d_b, d_y;
+ * act as snf_dense_layer (reference bottleneck.py:461-462 and the `f(Y.dot(W) + b)` of :485-500). */
+int snf_dense_layer_bf16(int device_id, const float* d_x, int64_t m, int32_t k, const uint16_t* d_packed,
+                         const float* d_b, int32_t n, int32_t act, float* d_y, void* stream);
+/* snf_bottleneck_forward (reference bottleneck.py:477-501) with W2, W3, W6 and W7 (h_params[2], [4], [8], [10])
+ * given as packed bfloat16 images and evaluated as snf_dense_layer_bf16; W1 and W5 (unbounded inputs, folded
+ * normalisations, the row gather) and every bias are float32 as there, and so are d_bn and d_out. */
+int snf_bottleneck_forward_bf16(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
+                                const int32_t* h_widths, const void* const* h_params, float* d_bn, float* d_out,
+                                void* stream);
 
 /* ---- CREPE pitch (reference processor/pitch_crepe.py, CrepePitchProcessor) -------------------------
  * The CREPE network on 16 kHz int16 audio: frames of 1024 samples every `hop`, a signal of n samples gives

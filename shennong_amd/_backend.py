@@ -44,7 +44,8 @@ EXPORTS = [
     'snf_gmm_selection_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
     'snf_affine_apply_segments', 'snf_vtln_gram_rows', 'snf_dense_layer', 'snf_bottleneck_vad',
     'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward', 'snf_crepe_conv',
-    'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot']
+    'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot', 'snf_packed_weights_bf16_size',
+    'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -172,6 +173,11 @@ def lib():
         L.snf_bottleneck_fbank.argtypes = [i32, vp, pi64, i64, vp, f32, C.c_uint64, vp, vp]
         L.snf_bottleneck_nn_input.argtypes = [i32, vp, vp, vp, pi64, i64, i32, vp, vp, vp]
         L.snf_bottleneck_forward.argtypes = [i32, vp, pi64, i64, pi32, C.POINTER(vp), vp, vp, vp]
+        L.snf_packed_weights_bf16_size.argtypes = [i32, i32]
+        L.snf_packed_weights_bf16_size.restype = i64
+        L.snf_pack_weights_bf16.argtypes = [i32, vp, i32, i32, vp, vp]
+        L.snf_dense_layer_bf16.argtypes = [i32, vp, i64, i32, vp, vp, i32, i32, vp, vp]
+        L.snf_bottleneck_forward_bf16.argtypes = [i32, vp, pi64, i64, pi32, C.POINTER(vp), vp, vp, vp]
         L.snf_crepe_conv.argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp]
         L.snf_crepe_forward.argtypes = [i32, vp, pi64, i64, i32, i32, pi32, C.POINTER(vp), vp, vp]
         L.snf_crepe_decode.argtypes = [i32, vp, pi64, i64, i32, vp, vp, vp, vp]

@@ -309,7 +309,7 @@ int snf_affine_apply_segments(int device_id, const float* d_x, int64_t n_frames,
 // ---- bottleneck extractor (kernels_bottleneck.hip) ------------------------------------------------------
 namespace {
 constexpr int kBnWin = 200, kBnShift = 80, kBnMel = 24, kBnIn = 144, kBnOut = 80, kBnEdge = 15, kBnStack = 5,
-              kBnStackStep = 5;
+              kBnStackStep = 5, kBnMaxWidth = 1 << 20;
 
 int bn_check_offsets(const int64_t* h_off, int64_t n, const char* what) {
   if (n < 0) return set_error(SNF_E_INVALID, std::string("bottleneck: number of utterances < 0"));
@@ -344,6 +344,43 @@ int snf_dense_layer(int device_id, const float* d_x, int64_t m, int32_t k, const
   int rc = lay.begin(device_id, stream);
   if (rc) return rc;
   rc = launch_bn_dense(d_x, m, k, d_w, d_b, n, act, d_y, nullptr, 0, 0, lay.s);
+  return lay.finish(rc, "dense layer kernel failed");
+}
+
+int64_t snf_packed_weights_bf16_size(int32_t k, int32_t n) {
+  if (k < 1 || n < 1 || k > kBnMaxWidth || n > kBnMaxWidth) return 0;
+  return int64_t(n) * bn_bf16_padded_k(k);
+}
+
+int snf_pack_weights_bf16(int device_id, const float* d_w, int32_t k, int32_t n, uint16_t* d_packed, void* stream) {
+  if (k < 1 || n < 1) return set_error(SNF_E_INVALID, "pack weights: k and n must be at least 1");
+  if (k > kBnMaxWidth || n > kBnMaxWidth) return set_error(SNF_E_INVALID, "pack weights: k and n must be at most 2^20");
+  if (!d_w || !d_packed) return set_error(SNF_E_INVALID, "pack weights: null buffer");
+  if (reinterpret_cast<uintptr_t>(d_packed) & 15)
+    return set_error(SNF_E_INVALID, "pack weights: the image is not 16-byte aligned");
+  Planless lay;
+  int rc = lay.begin(device_id, stream);
+  if (rc) return rc;
+  rc = launch_bn_pack_bf16(d_w, k, n, d_packed, lay.s);
+  return lay.finish(rc, "pack weights kernel failed");
+}
+
+int snf_dense_layer_bf16(int device_id, const float* d_x, int64_t m, int32_t k, const uint16_t* d_packed,
+                         const float* d_b, int32_t n, int32_t act, float* d_y, void* stream) {
+  if (m < 0) return set_error(SNF_E_INVALID, "dense layer: number of rows < 0");
+  if (k < 1 || n < 1) return set_error(SNF_E_INVALID, "dense layer: k and n must be at least 1");
+  if (k > kBnMaxWidth || n > kBnMaxWidth) return set_error(SNF_E_INVALID, "dense layer: k and n must be at most 2^20");
+  if (act != 0 && act != 1) return set_error(SNF_E_INVALID, "dense layer: act must be 0 (identity) or 1 (sigmoid)");
+  if (!d_packed || !d_b) return set_error(SNF_E_INVALID, "dense layer: null weights or bias");
+  if (reinterpret_cast<uintptr_t>(d_packed) & 15)
+    return set_error(SNF_E_INVALID, "dense layer: packed weights are not 16-byte aligned");
+  if (m > 0 && (!d_x || !d_y)) return set_error(SNF_E_INVALID, "dense layer: null buffer");
+  if (m > (int64_t(1) << 40) / std::max(k, n)) return set_error(SNF_E_INVALID, "dense layer: matrix too large");
+  if (m == 0) return SNF_OK;
+  Planless lay;
+  int rc = lay.begin(device_id, stream);
+  if (rc) return rc;
+  rc = launch_bn_dense_bf16(d_x, m, k, d_packed, d_b, n, act, d_y, lay.s);
   return lay.finish(rc, "dense layer kernel failed");
 }
 
@@ -422,9 +459,10 @@ int snf_bottleneck_nn_input(int device_id, const float* d_logmel, const uint8_t*
   return lay.finish(rc, "bottleneck input kernels failed");
 }
 
-int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
-                           const int32_t* h_widths, const float* const* h_params, float* d_bn, float* d_out,
-                           void* stream) {
+namespace {
+// the stacked networks; `bf16`: W2, W3, W6 and W7 are packed bfloat16 images and run on bn_dense_bf16_kernel
+int bn_forward(bool bf16, int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
+               const int32_t* h_widths, const void* const* h_params, float* d_bn, float* d_out, void* stream) {
   int rc = bn_check_offsets(h_row_offsets, n_utts, "row");
   if (rc) return rc;
   if (!h_widths || !h_params) return set_error(SNF_E_INVALID, "bottleneck: null layer description");
@@ -433,6 +471,10 @@ int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row
       return set_error(SNF_E_INVALID, "bottleneck: layer width " + std::to_string(i) + " out of range");
   for (int i = 0; i < 12; ++i)
     if (!h_params[i]) return set_error(SNF_E_INVALID, "bottleneck: null parameter buffer " + std::to_string(i));
+  if (bf16)
+    for (int i : {2, 4, 8, 10})
+      if (reinterpret_cast<uintptr_t>(h_params[i]) & 15)
+        return set_error(SNF_E_INVALID, "bottleneck: packed weights " + std::to_string(i) + " are not 16-byte aligned");
   if (n_utts == 0) return SNF_OK;
   const int span = kBnStackStep * (kBnStack - 1);   // 20 rows of the first stage under one stacked row
   std::vector<int64_t> ooff(n_utts + 1, 0);
@@ -458,21 +500,42 @@ int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row
   if ((rc = lay.begin(device_id, stream))) return rc;
   SNF_HIP_CHECK(hipMemcpyAsync(d_roff, h_row_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, lay.s));
   SNF_HIP_CHECK(hipMemcpyAsync(d_ooff, ooff.data(), sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, lay.s));
-  const float* const* P = h_params;
+  const void* const* P = h_params;
+  auto F = [](const void* p) { return static_cast<const float*>(p); };
+  // a layer that reads sigmoid outputs: the float32 kernel or the bfloat16 one
+  auto hidden = [&](const float* x, int64_t m, int k, int i, int n, int act, float* y) {
+    return bf16 ? launch_bn_dense_bf16(x, m, k, static_cast<const uint16_t*>(P[i]), F(P[i + 1]), n, act, y, lay.s)
+                : launch_bn_dense(x, m, k, F(P[i]), F(P[i + 1]), n, act, y, nullptr, 0, 0, lay.s);
+  };
   for (int64_t a = 0; a < R0 && !rc; a += chunk) {
     const int64_t m = std::min(chunk, R0 - a);
-    rc = launch_bn_dense(d_x + a * kBnIn, m, kBnIn, P[0], P[1], h_widths[0], 1, h1, nullptr, 0, 0, lay.s);
-    if (!rc) rc = launch_bn_dense(h1, m, h_widths[0], P[2], P[3], h_widths[1], 1, h2, nullptr, 0, 0, lay.s);
-    if (!rc) rc = launch_bn_dense(h2, m, h_widths[1], P[4], P[5], kBnOut, 0, d_bn + a * kBnOut, nullptr, 0, 0, lay.s);
+    rc = launch_bn_dense(d_x + a * kBnIn, m, kBnIn, F(P[0]), F(P[1]), h_widths[0], 1, h1, nullptr, 0, 0, lay.s);
+    if (!rc) rc = hidden(h1, m, h_widths[0], 2, h_widths[1], 1, h2);
+    if (!rc) rc = hidden(h2, m, h_widths[1], 4, kBnOut, 0, d_bn + a * kBnOut);
   }
   if (!rc) rc = launch_bn_row_map(d_roff, d_ooff, n_utts, R1, d_map, lay.s);
   for (int64_t a = 0; a < R1 && !rc; a += chunk) {
     const int64_t m = std::min(chunk, R1 - a);
-    rc = launch_bn_dense(d_bn, m, kBnStack * kBnOut, P[6], P[7], h_widths[2], 1, h1, d_map + a, kBnOut, kBnStackStep, lay.s);
-    if (!rc) rc = launch_bn_dense(h1, m, h_widths[2], P[8], P[9], h_widths[3], 1, h2, nullptr, 0, 0, lay.s);
-    if (!rc) rc = launch_bn_dense(h2, m, h_widths[3], P[10], P[11], kBnOut, 0, d_out + a * kBnOut, nullptr, 0, 0, lay.s);
+    rc = launch_bn_dense(d_bn, m, kBnStack * kBnOut, F(P[6]), F(P[7]), h_widths[2], 1, h1, d_map + a, kBnOut, kBnStackStep,
+                         lay.s);
+    if (!rc) rc = hidden(h1, m, h_widths[2], 8, h_widths[3], 1, h2);
+    if (!rc) rc = hidden(h2, m, h_widths[3], 10, kBnOut, 0, d_out + a * kBnOut);
   }
   return lay.finish(rc, "bottleneck network kernels failed");
+}
+}  // namespace
+
+int snf_bottleneck_forward(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
+                           const int32_t* h_widths, const float* const* h_params, float* d_bn, float* d_out,
+                           void* stream) {
+  return bn_forward(false, device_id, d_x, h_row_offsets, n_utts, h_widths,
+                    reinterpret_cast<const void* const*>(h_params), d_bn, d_out, stream);
+}
+
+int snf_bottleneck_forward_bf16(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
+                                const int32_t* h_widths, const void* const* h_params, float* d_bn, float* d_out,
+                                void* stream) {
+  return bn_forward(true, device_id, d_x, h_row_offsets, n_utts, h_widths, h_params, d_bn, d_out, stream);
 }
 
 }  // extern "C"

@@ -19,6 +19,28 @@
 //     over rows of width gw: the five-frame stack of the second network (gw = 80, gs = 5) is read straight
 //     from the first network's output and never written to memory.
 //
+// bfloat16 dense layer (bn_dense_bf16_kernel): Y = act(bf16(A) bf16(W) + b) on v_mfma_f32_32x32x16_bf16, for the
+// layers that read sigmoid outputs (W2, W3, W6, W7).  A and Y are float32 in memory, the sums float32.
+//   * Weight image (bn_pack_bf16_kernel, once per network): Wt[n][kp] bfloat16, k-contiguous per output column,
+//     kp = K rounded up to the k tile of 64 and zero beyond K.  Lane l of the MFMA holds A[l & 31][8 (l >> 5) + j]
+//     and B[8 (l >> 5) + j][l & 31], j = 0..7: a B fragment is 8 consecutive k of one column, i.e. 16 contiguous
+//     bytes of the image, and an A fragment 8 consecutive k of one row.  No transpose anywhere.
+//   * Rounding: to nearest, ties to even, by v_cvt_pk_bf16_f32 (a NaN stays a NaN), for A in the loader before
+//     the LDS write and for W in the pack kernel, so operands that were rounded beforehand give the same bits.
+//     (The same rounding in integer arithmetic, about 7 instructions per element, was measured 10 % slower on the
+//     square layer at 1500.)
+//   * Block tile 128 x 128 x 64, 4 waves in 2 x 2, a wave owns 64 x 64 = 2 x 2 MFMA tiles; a k tile is 4 steps
+//     of 16 and costs a wave 16 ds_read_b128 for 16 MFMAs.  Both tiles sit in LDS as [row][k] with a row stride
+//     of 144 bytes (9 slots of 16): the 16 lanes that a ds_read_b128 serves together read one k chunk of 16 rows
+//     that differ modulo 16, and 9 r mod 16 is a bijection, so they fall on 16 different slots of the 256-byte
+//     bank row; the 8 lanes that a ds_write_b128 serves together write 128 contiguous bytes of one row.
+//   * Next tile prefetched into registers before the MFMAs (8 float4 of A, 4 uint4 of W), one LDS buffer, two
+//     barriers per tile, as bn_dense_kernel.  Tile rows beyond M and columns beyond N repeat the last valid one
+//     (no branch between the loads; rows and columns of a product do not mix and the epilogue stores neither);
+//     k beyond K is zero in both operands, and a zero product leaves a float32 sum as it is.
+//   * An element's value depends on its A row, its W column and K only (the MFMA's fixed summation order over
+//     the 16 k of a step, steps ascending), not on M, the row's place or the tiling: batch invariance as above.
+//
 // Front end (bn_fbank_kernel): 16 lanes per frame, 16 frames per workgroup.  200 samples (+ uniform dither
 // keyed by utterance and sample index), Hamming window, zero-extended to 256, complex 16 x 16 FFT (two
 // register fft16 around one LDS transpose), power of bins 0..128, 24 filters from the host-built table,
@@ -174,6 +196,170 @@ __global__ void __launch_bounds__(kThreads) bn_dense_kernel(const DenseArgs g, i
         g.y[row * g.N + c] = v;
       }
     }
+  }
+}
+
+// ---- bfloat16 dense layer -------------------------------------------------------------------------------
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kQK = 64;     // k tile of the bfloat16 kernel: the weight image pads K to a multiple of it
+constexpr unsigned kXcds = 8;
+constexpr int kQLd = 72;    // bfloat16 per tile row in LDS (144 bytes = 9 slots of 16)
+
+struct DenseBf16Args {
+  const float* x;
+  const uint16_t* wt;   // packed weights Wt[N][Kp]
+  const float* b;
+  float* y;
+  int64_t M;
+  int K, Kp, N, act;
+};
+
+// float32 -> bfloat16 by the hardware's conversion (v_cvt_pk_bf16_f32: to nearest, ties to even, subnormals
+// kept, a NaN stays a NaN); one function for both operands
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint16_t bf16_rne(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
+
+__device__ __forceinline__ uint32_t bf16_pack2(float lo, float hi) {
+  f32x2 v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+
+// 4 consecutive k of row `row` (< M) of x, zeros outside K.  kVec (K a multiple of 4, x 16-byte aligned): one
+// unconditional 16-byte load from a clamped address and a select, so that no branch separates the loads of a tile
+template <bool kVec>
+__device__ __forceinline__ float4 load_q4(const DenseBf16Args& g, int64_t row, int k) {
+  if (kVec) {
+    const float4 t = *reinterpret_cast<const float4*>(g.x + row * g.K + min(k, g.K - 4));
+    return k < g.K ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (k >= g.K) return v;
+  const float* p = g.x + row * g.K + k;
+  v.x = p[0];
+  if (k + 1 < g.K) v.y = p[1];
+  if (k + 2 < g.K) v.z = p[2];
+  if (k + 3 < g.K) v.w = p[3];
+  return v;
+}
+
+// 8 consecutive k of column n (< N) of the packed weights (k < Kp always: the image is padded)
+__device__ __forceinline__ uint4 load_w8(const DenseBf16Args& g, int n, int k) {
+  return *reinterpret_cast<const uint4*>(g.wt + static_cast<int64_t>(n) * g.Kp + k);
+}
+
+template <bool kVec>
+__global__ void __launch_bounds__(kThreads, 3) bn_dense_bf16_kernel(const DenseBf16Args g, int n_tiles_n) {
+  __shared__ __attribute__((aligned(16))) uint16_t As[kBM * kQLd];
+  __shared__ __attribute__((aligned(16))) uint16_t Bs[kBN * kQLd];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
+  // Workgroups go to the 8 XCDs in turn, each with an L2 of its own: give every XCD a contiguous run of tiles,
+  // so that the tiles_n workgroups that share a block of A rows meet in one L2 (measured + 5 to 8 % on the
+  // square layers at 500 and 1500 against the plain order, same bits).  A bijection of the workgroup ids.
+  const unsigned nwg = gridDim.x, xcd = blockIdx.x % kXcds, q = nwg / kXcds, r = nwg % kXcds;
+  const unsigned id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blockIdx.x / kXcds;
+  const int64_t m0 = static_cast<int64_t>(id / n_tiles_n) * kBM;
+  const int n0 = static_cast<int>(id % n_tiles_n) * kBN;
+  // loader coordinates, the same for both operands: tile rows l_r + 32 i, k 8 l_c .. 8 l_c + 7
+  const int l_c = tid & 7, l_r = tid >> 3;
+  // tile rows beyond M and columns beyond N repeat the last one: rows and columns of a product do not mix,
+  // and the epilogue stores neither
+  int64_t a_row[4];
+  int b_col[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    a_row[i] = min(m0 + l_r + 32 * i, g.M - 1);
+    b_col[i] = min(n0 + l_r + 32 * i, g.N - 1);
+  }
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+  float4 ra[4][2];
+  uint4 rb[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ra[i][0] = load_q4<kVec>(g, a_row[i], 8 * l_c);
+    ra[i][1] = load_q4<kVec>(g, a_row[i], 8 * l_c + 4);
+    rb[i] = load_w8(g, b_col[i], 8 * l_c);
+  }
+  const uint16_t* pa = As + (wm * 64 + li) * kQLd + 8 * lh;
+  const uint16_t* pb = Bs + (wn * 64 + li) * kQLd + 8 * lh;
+  for (int k0 = 0; k0 < g.K; k0 += kQK) {
+    __syncthreads();   // the previous tile's operand reads are done
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      uint4 q;
+      q.x = bf16_pack2(ra[i][0].x, ra[i][0].y);
+      q.y = bf16_pack2(ra[i][0].z, ra[i][0].w);
+      q.z = bf16_pack2(ra[i][1].x, ra[i][1].y);
+      q.w = bf16_pack2(ra[i][1].z, ra[i][1].w);
+      *reinterpret_cast<uint4*>(As + (l_r + 32 * i) * kQLd + 8 * l_c) = q;
+      *reinterpret_cast<uint4*>(Bs + (l_r + 32 * i) * kQLd + 8 * l_c) = rb[i];
+    }
+    __syncthreads();
+    if (k0 + kQK < g.K) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ra[i][0] = load_q4<kVec>(g, a_row[i], k0 + kQK + 8 * l_c);
+        ra[i][1] = load_q4<kVec>(g, a_row[i], k0 + kQK + 8 * l_c + 4);
+        rb[i] = load_w8(g, b_col[i], k0 + kQK + 8 * l_c);
+      }
+    }
+    // always the whole tile: beyond K both operands are zeros in LDS, and a zero product leaves a sum as it is
+#pragma unroll
+    for (int s = 0; s < kQK / 16; ++s) {
+      const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(pa + 16 * s);
+      const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(pa + 32 * kQLd + 16 * s);
+      const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(pb + 16 * s);
+      const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(pb + 32 * kQLd + 16 * s);
+      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
+      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
+      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
+      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
+    }
+  }
+  // epilogue: bias, activation, one store per element (as bn_dense_kernel)
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn) {
+    const int c = n0 + wn * 64 + tn * 32 + li;
+    if (c >= g.N) continue;
+    const float bias = g.b[c];
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        if (row >= g.M) continue;
+        float v = acc[tm][tn][r] + bias;
+        if (g.act) v = bn_sigmoid(v);
+        g.y[row * g.N + c] = v;
+      }
+    }
+  }
+}
+
+// wt[n][k] = bfloat16(w[k][n]) for k < K, 0 for K <= k < Kp: 32 x 32 tiles transposed through LDS
+__global__ void __launch_bounds__(kThreads) bn_pack_bf16_kernel(const float* __restrict__ w, int K, int N, int Kp,
+                                                               uint16_t* __restrict__ wt) {
+  __shared__ uint16_t tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int k0 = static_cast<int>(blockIdx.x) * 32, n0 = static_cast<int>(blockIdx.y) * 32;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int k = k0 + ty + 8 * i, n = n0 + tx;
+    tile[ty + 8 * i][tx] = (k < K && n < N) ? bf16_rne(w[static_cast<int64_t>(k) * N + n]) : uint16_t(0);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int n = n0 + ty + 8 * i, k = k0 + tx;
+    if (n < N && k < Kp) wt[static_cast<int64_t>(n) * Kp + k] = tile[tx][ty + 8 * i];
   }
 }
 
@@ -462,6 +648,31 @@ int launch_bn_dense(const float* x, int64_t M, int K, const float* w, const floa
   if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "dense layer: too many tiles for one launch");
   hipLaunchKernelGGL(bn_dense_kernel, dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g,
                      tiles_n);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+int bn_bf16_padded_k(int K) { return (K + kQK - 1) / kQK * kQK; }
+
+int launch_bn_pack_bf16(const float* w, int K, int N, uint16_t* wt, hipStream_t stream) {
+  const int Kp = bn_bf16_padded_k(K);
+  hipLaunchKernelGGL(bn_pack_bf16_kernel, dim3(blocks(Kp, 32), blocks(N, 32)), dim3(kThreads), 0, stream, w, K, N, Kp,
+                     wt);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+int launch_bn_dense_bf16(const float* x, int64_t M, int K, const uint16_t* wt, const float* b, int N, int act,
+                         float* y, hipStream_t stream) {
+  if (M <= 0) return SNF_OK;
+  DenseBf16Args g;
+  g.x = x; g.wt = wt; g.b = b; g.y = y; g.M = M; g.K = K; g.Kp = bn_bf16_padded_k(K); g.N = N; g.act = act;
+  const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && K % 4 == 0;
+  const int64_t tiles_m = (M + kBM - 1) / kBM;
+  const int tiles_n = (N + kBN - 1) / kBN;
+  if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "dense layer: too many tiles for one launch");
+  hipLaunchKernelGGL(vec ? bn_dense_bf16_kernel<true> : bn_dense_bf16_kernel<false>,
+                     dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g, tiles_n);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
 }

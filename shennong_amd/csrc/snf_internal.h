@@ -396,6 +396,12 @@ int bn_max_context();
 // y = act(A w + b); `a_row` non-null: A[r][k] = x[(a_row[r] + gs (k / gw)) * gw + k % gw]
 int launch_bn_dense(const float* x, int64_t M, int K, const float* w, const float* b, int N, int act, float* y,
                     const int64_t* a_row, int gw, int gs, hipStream_t stream);
+// bfloat16 layer: wt[N][Kp] is the packed image of w[K][N], Kp = bn_bf16_padded_k(K), 16-byte aligned
+int bn_bf16_padded_k(int K);
+int launch_bn_pack_bf16(const float* w, int K, int N, uint16_t* wt, hipStream_t stream);
+// y = act(bf16(x) bf16(w) + b), float32 accumulation, float32 y
+int launch_bn_dense_bf16(const float* x, int64_t M, int K, const uint16_t* wt, const float* b, int N, int act,
+                         float* y, hipStream_t stream);
 int launch_bn_row_map(const int64_t* in_off, const int64_t* out_off, int64_t n_utts, int64_t rows, int64_t* a_row,
                       hipStream_t stream);
 int launch_bn_fbank(const int16_t* wave, const int64_t* soff, const int64_t* foff, int64_t n_utts,

@@ -10,6 +10,11 @@ numpy there); here every stage is a HIP kernel (``kernels_bottleneck.hip``): the
 FP32 matrix cores with bias and activation fused, and ``process_all`` is one batched launch per kernel
 over all utterances.
 
+Beyond the reference: the attribute :attr:`BottleneckProcessor.precision` (``'float32'`` by default) selects
+a bfloat16 matrix-core path for the four layers that read sigmoid outputs (``W2``, ``W3``, ``W6``, ``W7``):
+their activations and weights are rounded to bfloat16 (to nearest, ties to even) at the layer's input and the
+products accumulated in float32; everything else is the float32 path unchanged.
+
 Weights: the three published networks *BabelMulti*, *FisherMono* and *FisherTri* are ``.npz`` files of 17
 arrays that are not shipped with this package.  They are looked up under their published names in the
 directory named by the environment variable ``SHENNONG_AMD_BOTTLENECK_DIR`` and then in
@@ -53,6 +58,8 @@ _WIN, _SHIFT, _NFFT, _NMEL, _NBASES, _EDGE, _NDIMS, _STACK = 200, 80, 256, 24, 6
 _NIN = _NMEL * _NBASES
 _MAX_CONTEXT = 64
 _DITHER_SEED = 0x5EED0B0771E9EC
+PRECISIONS = ('float32', 'bfloat16')
+_PACKED = (2, 4, 8, 10)    # W2, W3, W6, W7 among the twelve parameters: the layers of the bfloat16 path
 
 _LOCK = threading.Lock()
 _LOADED = {}    # (name, file) -> validated host parameters
@@ -168,8 +175,37 @@ class _DeviceNetwork:
             buf = _backend.DeviceBuffer(max(16, a.nbytes), device)
             buf.upload(a)
             self.buffers.append(buf)
+        self.device = device
         self.pointers = (C.c_void_p * 12)(*[b.ptr for b in self.buffers])
         self.widths = (C.c_int32 * 4)(*net.widths)
+        self._packed = None
+
+    def packed_pointers(self):
+        """The twelve pointers with W2, W3, W6 and W7 as packed bfloat16 images (built on first use and kept
+        beside the float32 weights)"""
+        with _LOCK:
+            if self._packed is None:
+                pointers = [b.ptr for b in self.buffers]
+                images = []
+                for i in _PACKED:
+                    images.append(pack_weights(self.buffers[i], *self.net.params[i].shape, self.device))
+                    pointers[i] = images[-1].ptr
+                self._packed = (images, (C.c_void_p * 12)(*pointers))
+            return self._packed[1]
+
+
+def _check_precision(value):
+    if value not in PRECISIONS:
+        raise ValueError('invalid precision "{}", choose in "{}"'.format(value, ', '.join(PRECISIONS)))
+    return value
+
+
+def pack_weights(w, k, n, device):
+    """The packed bfloat16 image (a DeviceBuffer) of the float32 matrix [k, n] in the DeviceBuffer `w`"""
+    L = _backend.lib()
+    image = _backend.DeviceBuffer(max(16, 2 * int(L.snf_packed_weights_bf16_size(k, n))), device)
+    _backend.check(L.snf_pack_weights_bf16(device, _p(w), k, n, _p(image), None))
+    return image
 
 
 def _device_array(key, build, device):
@@ -236,8 +272,10 @@ class BottleneckBatch:
     def host_logmel(self):
         return self.logmel.download(np.empty((self.total_frames, _NMEL), dtype=np.float32))
 
-    def forward(self, dnet):
-        """Context projection and the two networks; returns the features [total rows, 80] float32 (host)"""
+    def forward(self, dnet, precision='float32'):
+        """Context projection and the two networks; returns the features [total rows, 80] float32 (host).
+        `precision` 'bfloat16': W2, W3, W6 and W7 on the bfloat16 matrix cores"""
+        _check_precision(precision)
         context = dnet.net.context
         basis = _device_array((self.device, context), lambda: _context_basis(context), self.device)
         rows = self.frames + 2 * _EDGE - 2 * context
@@ -253,17 +291,25 @@ class BottleneckBatch:
             _p(basis), _p(self.x), None))
         self.bn = _backend.DeviceBuffer(max(16, 4 * _NDIMS * r0), self.device)
         self.out = _backend.DeviceBuffer(max(16, 4 * _NDIMS * r1), self.device)
-        _backend.check(L.snf_bottleneck_forward(
-            self.device, _p(self.x), _off(self.roff), self.n, dnet.widths, dnet.pointers, _p(self.bn),
-            _p(self.out), None))
+        if precision == 'bfloat16':
+            _backend.check(L.snf_bottleneck_forward_bf16(
+                self.device, _p(self.x), _off(self.roff), self.n, dnet.widths, dnet.packed_pointers(), _p(self.bn),
+                _p(self.out), None))
+        else:
+            _backend.check(L.snf_bottleneck_forward(
+                self.device, _p(self.x), _off(self.roff), self.n, dnet.widths, dnet.pointers, _p(self.bn),
+                _p(self.out), None))
         return self.out.download(np.empty((r1, _NDIMS), dtype=np.float32))
 
     def host_bn(self):
         return self.bn.download(np.empty((int(self.roff[-1]), _NDIMS), dtype=np.float32))
 
 
-def dense_layer(x, w, b, act='identity', device=None):
-    """``act(x @ w + b)`` on the device through ``snf_dense_layer`` (float32 host arrays in and out)"""
+def dense_layer(x, w, b, act='identity', device=None, precision='float32'):
+    """``act(x @ w + b)`` on the device through ``snf_dense_layer`` (float32 host arrays in and out); with
+    `precision` 'bfloat16' through ``snf_pack_weights_bf16`` and ``snf_dense_layer_bf16``: `x` and `w` rounded
+    to bfloat16 on the device, float32 accumulation, bias, activation and result"""
+    _check_precision(precision)
     x = np.ascontiguousarray(x, dtype=np.float32)
     w = np.ascontiguousarray(w, dtype=np.float32)
     b = np.ascontiguousarray(b, dtype=np.float32)
@@ -275,9 +321,15 @@ def dense_layer(x, w, b, act='identity', device=None):
         bufs.append(_backend.DeviceBuffer(max(16, a.nbytes), device))
         bufs[-1].upload(a)
     y = _backend.DeviceBuffer(max(16, 4 * x.shape[0] * w.shape[1]), device)
-    _backend.check(_backend.lib().snf_dense_layer(
-        device, _p(bufs[0]), x.shape[0], x.shape[1], _p(bufs[1]), _p(bufs[2]), w.shape[1],
-        {'identity': 0, 'sigmoid': 1}[act], _p(y), None))
+    if precision == 'bfloat16':
+        image = pack_weights(bufs[1], w.shape[0], w.shape[1], device)
+        _backend.check(_backend.lib().snf_dense_layer_bf16(
+            device, _p(bufs[0]), x.shape[0], x.shape[1], _p(image), _p(bufs[2]), w.shape[1],
+            {'identity': 0, 'sigmoid': 1}[act], _p(y), None))
+    else:
+        _backend.check(_backend.lib().snf_dense_layer(
+            device, _p(bufs[0]), x.shape[0], x.shape[1], _p(bufs[1]), _p(bufs[2]), w.shape[1],
+            {'identity': 0, 'sigmoid': 1}[act], _p(y), None))
     return y.download(np.empty((x.shape[0], w.shape[1]), dtype=np.float32))
 
 
@@ -297,11 +349,15 @@ class BottleneckProcessor(FeaturesProcessor):
         If the `weights` are invalid
     RuntimeError
         If no weights file can be found
+
+    Beyond the reference, the attribute :attr:`precision` (not a constructor parameter) selects how the hidden
+    layers are computed.
     """
     def __init__(self, weights='BabelMulti', dither=0.1):
         super().__init__()
         self.weights = weights
         self.dither = dither
+        self._precision = 'float32'
         self._network()
 
     @property
@@ -328,6 +384,23 @@ class BottleneckProcessor(FeaturesProcessor):
         if value not in available:
             raise ValueError('invalid weights "{}", choose in "{}"'.format(value, ', '.join(sorted(available.keys()))))
         self._weights = value
+
+    @property
+    def precision(self):
+        """'float32' (default) or 'bfloat16': with 'bfloat16' the layers W2, W3, W6 and W7 round their
+        activations and weights to bfloat16 and run on the bfloat16 matrix cores (float32 accumulation, bias,
+        sigmoid and output); the features differ from the float32 ones by about 3e-3"""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        self._precision = _check_precision(value)
+
+    def get_properties(self, **kwargs):
+        """The processor's properties; they record the precision when it is not the default"""
+        if self._precision != 'float32':
+            kwargs.setdefault('precision', self._precision)
+        return super().get_properties(**kwargs)
 
     @property
     def ndims(self):
@@ -450,7 +523,7 @@ class BottleneckProcessor(FeaturesProcessor):
                 raise RuntimeError('no voice detected in signal{}, failed to extract features'.format(label(i)))
             self.log.debug('%d frames of speech detected (on %d total frames)', count, batch.frames[i])
         batch.fbank(self.dither)
-        out = batch.forward(dnet)
+        out = batch.forward(dnet, self._precision)
         _backend._check_finite(out)
         properties = self.get_properties()
         return [Features(out[a:b], self.times(b - a), properties, validate=False)

@@ -1,12 +1,16 @@
 #!/usr/bin/env python
 """Times the bottleneck extractor on one MI355X: per-stage device times (events around each C ABI call on
-device-resident audio), the whole ``process_all`` host to host, the achieved FP32 TFLOP/s of the two square
-layers (``snf_dense_layer`` alone, best of `--repeat`) and of the whole forward pass against the 157.3 TF
-FP32 matrix peak, and the ratio to the float64 numpy statement (tests/bottleneck_f64.py) on the host's CPUs.
+device-resident audio), the whole ``process_all`` host to host, the achieved TFLOP/s of the square layer
+(``snf_dense_layer`` / ``snf_dense_layer_bf16`` alone, best of `--repeat`) and of the whole forward pass
+against the matrix peak of the precision (157.3 TF FP32, 2516.6 TF BF16), and the ratio to the float64 numpy
+statement (tests/bottleneck_f64.py) on the host's CPUs.
 
-    python tools/time_bottleneck.py --utts 1000 --hidden 500 1500 [--seconds 3] [--out FILE]
+    python tools/time_bottleneck.py --utts 1000 --hidden 500 1500 [--precision float32 bfloat16] [--seconds 3]
+                                    [--out FILE]
 
-Prints one JSON line per configuration.  Synthetic weights (tests/bottleneck_f64.py make_weights)."""
+Prints one JSON line per configuration and precision; the precisions of one configuration are timed in one
+process on the same inputs (random operands), each after its own warm-up.  Synthetic weights
+(tests/bottleneck_f64.py make_weights)."""
 import argparse
 import ctypes as C
 import json
@@ -22,7 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 import bottleneck_f64 as f64  # noqa: E402
 
-PEAK_TF = 157.3
+PEAK_TF = {'float32': 157.3, 'bfloat16': 2516.6}   # 256 CUs x 4 SIMDs x 2.4 GHz x 64 (FP32) or 1024 (BF16) FLOP/clk
 
 
 def corpus(n, seconds, seed=0):
@@ -49,6 +53,7 @@ def main():
     ap.add_argument('--utts', type=int, nargs='+', default=[1000])
     ap.add_argument('--hidden', type=int, nargs='+', default=[500, 1500])
     ap.add_argument('--seconds', type=float, default=3.0)
+    ap.add_argument('--precision', nargs='+', default=['float32'], choices=['float32', 'bfloat16'])
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--cpu-utts', type=int, default=8)
     ap.add_argument('--out', default=None)
@@ -71,41 +76,53 @@ def main():
         x.upload(rng.uniform(0, 1, (m, hidden)).astype(np.float32))
         L = _backend.lib()
 
-        def square():
-            _backend.check(L.snf_dense_layer(_backend.get_device(), C.c_void_p(x.ptr), m, hidden,
-                                             C.c_void_p(dnet.buffers[2].ptr), C.c_void_p(dnet.buffers[3].ptr),
-                                             hidden, 1, C.c_void_p(y.ptr), None))
-        square()
-        sq = timed(square, args.repeat)
+        packed = bottleneck.pack_weights(dnet.buffers[2], hidden, hidden, _backend.get_device())
+
+        def square(precision):
+            if precision == 'bfloat16':
+                _backend.check(L.snf_dense_layer_bf16(_backend.get_device(), C.c_void_p(x.ptr), m, hidden,
+                                                      C.c_void_p(packed.ptr), C.c_void_p(dnet.buffers[3].ptr),
+                                                      hidden, 1, C.c_void_p(y.ptr), None))
+            else:
+                _backend.check(L.snf_dense_layer(_backend.get_device(), C.c_void_p(x.ptr), m, hidden,
+                                                 C.c_void_p(dnet.buffers[2].ptr), C.c_void_p(dnet.buffers[3].ptr),
+                                                 hidden, 1, C.c_void_p(y.ptr), None))
+        sq = {}
+        for precision in args.precision:
+            square(precision)
+            sq[precision] = timed(lambda: square(precision), args.repeat)
         for n in args.utts:
             waves = corpus(n, args.seconds)
             batch = bottleneck.BottleneckBatch(waves)
-            batch.vad(); batch.fbank(0.0); batch.forward(dnet)   # warm-up (scratch, tables)
+            batch.vad(); batch.fbank(0.0)   # warm-up (scratch, tables)
             t_vad = timed(batch.vad, args.repeat)
             t_fb = timed(lambda: batch.fbank(0.0), args.repeat)
-            t_fw = timed(lambda: batch.forward(dnet), args.repeat)
-            r0, r1 = int(batch.roff[-1]), int(batch.ooff[-1])
-            flop = 2.0 * (r0 * (144 * hidden + hidden * hidden + hidden * 80)
-                          + r1 * (400 * hidden + hidden * hidden + hidden * 80))
             utts = Utterances([('u%05d' % i, Audio(w, 8000, validate=False)) for i, w in enumerate(waves)])
-            proc.process_all(utts)
-            t_all = timed(lambda: proc.process_all(utts), args.repeat)
             k = min(args.cpu_utts, n)
             t0 = time.perf_counter()
             for w in waves[:k]:
                 f64.extract(w, weights)
             t_cpu = (time.perf_counter() - t0) / k * n
-            lines.append({
-                'hidden': hidden, 'utts': n, 'seconds_each': args.seconds, 'device': _backend.device_name(),
-                'vad_ms': 1e3 * t_vad, 'fbank_ms': 1e3 * t_fb,
-                'nn_input_forward_download_ms': 1e3 * t_fw, 'process_all_ms': 1e3 * t_all,
-                'forward_flop': flop, 'forward_tflops_incl_input_and_download': flop / t_fw / 1e12,
-                'square_layer_rows': m, 'square_layer_ms': 1e3 * sq,
-                'square_layer_tflops': 2.0 * m * hidden * hidden / sq / 1e12,
-                'square_layer_fraction_of_peak': 2.0 * m * hidden * hidden / sq / 1e12 / PEAK_TF,
-                'numpy_f64_ms_extrapolated_from': k, 'numpy_f64_ms': 1e3 * t_cpu,
-                'speedup_vs_numpy_f64': t_cpu / t_all})
-            print(json.dumps(lines[-1]), flush=True)
+            for precision in args.precision:
+                batch.forward(dnet, precision)
+                t_fw = timed(lambda: batch.forward(dnet, precision), args.repeat)
+                r0, r1 = int(batch.roff[-1]), int(batch.ooff[-1])
+                flop = 2.0 * (r0 * (144 * hidden + hidden * hidden + hidden * 80)
+                              + r1 * (400 * hidden + hidden * hidden + hidden * 80))
+                proc.precision = precision
+                proc.process_all(utts)
+                t_all = timed(lambda: proc.process_all(utts), args.repeat)
+                tf = 2.0 * m * hidden * hidden / sq[precision] / 1e12
+                lines.append({
+                    'precision': precision, 'hidden': hidden, 'utts': n, 'seconds_each': args.seconds,
+                    'device': _backend.device_name(), 'vad_ms': 1e3 * t_vad, 'fbank_ms': 1e3 * t_fb,
+                    'nn_input_forward_download_ms': 1e3 * t_fw, 'process_all_ms': 1e3 * t_all,
+                    'forward_flop': flop, 'forward_tflops_incl_input_and_download': flop / t_fw / 1e12,
+                    'square_layer_rows': m, 'square_layer_ms': 1e3 * sq[precision],
+                    'square_layer_tflops': tf, 'square_layer_fraction_of_peak': tf / PEAK_TF[precision],
+                    'numpy_f64_ms_extrapolated_from': k, 'numpy_f64_ms': 1e3 * t_cpu,
+                    'speedup_vs_numpy_f64': t_cpu / t_all})
+                print(json.dumps(lines[-1]), flush=True)
     if args.out:
         with open(args.out, 'w') as fh:
             for line in lines:
