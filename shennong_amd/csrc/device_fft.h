@@ -118,6 +118,39 @@ __device__ __forceinline__ void read_quads_whole(const void* base, float4 (&dst)
     dst[i] = make_float4(v.x, v.y, v.z, v.w);
   }
 }
+// Operand reads that are ISSUED in one place and USED in another (fbank512b_kernel: the constant operands of the mel
+// chain are requested in front of the power-tile writes).  A read whose wait stands in a later asm statement is
+// not safe (see above), so these are volatile accesses: each stays one LDS instruction where it stands, in program
+// order with the asm statements and the other volatile accesses around it, and the COMPILER knows it is in flight
+// and waits before the first use.  land_quad makes that one wait for a whole batch: the LDS returns a wave's reads
+// in order, so once the last quad of a batch has landed in front of a scheduling barrier, every earlier read has.
+//   dst[i] = the float4 at `base` + i * STRIDE float4, i < N
+template <int N, int STRIDE, int M>
+__device__ __forceinline__ void issue_quads(const void* base, float4 (&dst)[M]) {
+  static_assert(N <= M, "more reads than registers");
+  typedef float f32x4v __attribute__((ext_vector_type(4)));
+  typedef const volatile f32x4v __attribute__((address_space(3))) * lds_quad_ptr;
+  lds_quad_ptr q = (lds_quad_ptr)(__builtin_assume_aligned(base, 16));
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const f32x4v v = q[i * STRIDE];
+    dst[i] = make_float4(v.x, v.y, v.z, v.w);
+  }
+}
+//   dst[i] = the float at `base` + i * STRIDE floats, i < N
+template <int N, int STRIDE, int M>
+__device__ __forceinline__ void issue_floats(const void* base, float (&dst)[M]) {
+  static_assert(N <= M, "more reads than registers");
+  typedef const volatile float __attribute__((address_space(3))) * lds_float_ptr;
+  lds_float_ptr q = (lds_float_ptr)(base);
+#pragma unroll
+  for (int i = 0; i < N; ++i) dst[i] = q[i * STRIDE];
+}
+__device__ __forceinline__ void land_quad(float4& last) {
+  // (in / out operands: as inputs alone they cost the MFCC forms two registers more and some of them a spill)
+  asm volatile("" : "+v"(last.x), "+v"(last.y), "+v"(last.z), "+v"(last.w));
+  __builtin_amdgcn_sched_barrier(0);
+}
 // counter-based N(0,1) pair for Kaldi's per-frame dither (statistical stand-in for RandGauss(), which
 // draws from C rand() and is not reproducible): murmur-style 32-bit finalisers + Box-Muller on the
 // hardware log2 / sqrt / sin / cos (v_sin_f32 and v_cos_f32 take revolutions)

@@ -15,8 +15,8 @@
 //     the 0.40 ms its loads and stores take.  Fewer and cheaper instructions are the only lever.
 //   * Hence: the set index lives in scalar registers (wid through v_readfirstlane: the 64-bit address
 //     arithmetic leaves the vector pipe); the MFMA chain is as long as the widest part of the bank plan
-//     (28 instructions for 40 bins, 24 for 23, instead of a padded 32) with every operand read issued
-//     before its first instruction; and the rows leave through ONE unconditional buffer store per set:
+//     (28 instructions for 40 bins, 24 for 23, instead of a padded 32); and the rows leave through ONE
+//     unconditional buffer store per set:
 //     with the stores inside `if`s the compiler cannot count the vector-memory operations behind the
 //     prefetched samples, waits with vmcnt(0) at the top of every iteration, and the wave sits there
 //     until the stores of the previous set are acknowledged (1300-2000 of 11 000 clocks per iteration).
@@ -72,7 +72,18 @@ constexpr int kTileBytes = 16 * kTileRow * 8;  // wave-private LDS per frame (21
 // 512-point window).  Without the `+ 0` of the full first layer the compiler contracts other multiply / add
 // pairs around the butterflies than it does in fbank512_kernel: 4.5 % of the outputs differed in the last bits
 // (up to 3e-5), with and without the forwarded products pinned (tools/experiments/fbank512b_prune_pass1.diff).
-template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER>
+// Operand reads ahead of their chains (NJ = 13; profiles/NOTEBOOK.md 4.1e, profiles/fbank512b_tail_*).  "Every operand
+// read issued before the chain" was what the source said, not what the compiler made of it: with the reads left to
+// the scheduler the listing held five ds_read_b128 in front of the first MFMA, the other nine between the quads
+// (each about four MFMAs ahead of its use) and the seventh quad behind a branch with two reads and a full
+// s_waitcnt of its own - an LDS round trip inside the chain in every set.  Now the bank plan is a template
+// parameter of the launch (MMQ = 7 / 6 quads, LV = 3 / 4 blocks per split group; launch_plan) and the reads are
+// volatile accesses, which stay where they stand: the constant operands (weights, 0 / 1 factors) in FRONT of the
+// power-tile writes, the tile operands in one batch behind them, one s_waitcnt, then 28 / 24 MFMAs with no LDS
+// instruction and no wait between them.  The MFCC tail requests its six constant DCT rows in front of the logs and
+// the log-mel write and keeps the lifter of the lane in a register.  Every other plan, the NJ = 16 forms and the
+// few NJ = 13 forms that have no registers for it (launch_plan) run the code of before (MMQ = 0).
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV>
 __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512Params p, const BatchArgs b,
                                                                   float* __restrict__ out,
                                                                   double* __restrict__ energy_out) {
@@ -116,6 +127,13 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     mm_start_once = reinterpret_cast<const int*>(mm_lane)[0];
     mm_out_once = reinterpret_cast<const int*>(mm_lane)[64];
   }
+  // MMQ = 7 / 6: the chain length is known at compile time (launch_plan) and the operands of the whole chain are
+  // read ahead of it (phases E and F below); LV = 3 / 4: so is the number of blocks a wide group is split into
+  static_assert(MMQ == 0 || (NJ == 13 && (MMQ == 6 || MMQ == 7) && (LV == 3 || LV == 4)), "plans of launch_plan");
+  const float4* __restrict__ mm_b_once = reinterpret_cast<const float4*>(mtile + mm_start_once);
+  // (MFCC: the lifter of the lane's cepstrum is a constant of the lane)
+  float lifter_once = 1.0f;
+  if (NJ == 13 && KIND == SNF_KIND_MFCC) lifter_once = t_lifter[l];
 
   const float win_len_f = static_cast<float>(p.win_len), inv_win_len = 1.0f / win_len_f;
   const int64_t n_sets = (b.total_frames + 3) >> 2;
@@ -324,6 +342,15 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     }
     const float p128 = 4.0f * (z[8].x * z[8].x + z[8].y * z[8].y);  // k = 128: lane 0, register 8
     wave_lds_order();
+    // the constant operands of the mel phase (MMQ != 0): the weights of the whole chain and the 0 / 1 factors of
+    // the split groups are requested HERE, in front of the tile writes - the LDS serves a wave in order, so they
+    // land while the power tile is written and the chain below waits for the tile reads alone
+    float4 mm_w[7];
+    float mm_f[3] = {0.0f, 0.0f, 0.0f};
+    if (MMQ != 0) {
+      issue_quads<MMQ, 64>(t_mm_a + lane, mm_w);
+      issue_floats<LV - 1, 64>(mm_lane + 128, mm_f);
+    }
     // ---- E: power tile ------------------------------------------------------------------------------
     {
       // two rows per instruction (ds_write2_b32: 3 LDS-path clocks per dword against 4 for ds_write_b32)
@@ -343,6 +370,12 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     }
     wave_lds_order();
     __builtin_amdgcn_sched_barrier(0);
+    // ... and the tile operands of the whole chain directly behind the tile (MMQ != 0)
+    float4 mm_x[7];
+    if (MMQ != 0) {
+      issue_quads<MMQ, 1>(mm_b_once, mm_x);
+      __builtin_amdgcn_sched_barrier(0);
+    }
 
     // ---- log-energy column ---------------------------------------------------------------------------
     float log_energy = 0.0f;
@@ -375,9 +408,15 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     acc1 = __builtin_amdgcn_mfma_f32_4x4x1f32(A_.w, X_.w, acc1, 0, 0, 0);   \
   } while (0)
       const int n_quads = p.mm_quads;  // wave-uniform
-      if (n_quads == 7 || n_quads == 6) {
-        // the common shapes (40 / 23 bins at 16 kHz): every operand read is issued before the first
-        // instruction of the chain, which then runs at the pace of the matrix pipe
+      if (MMQ != 0) {
+        // the common shapes (40 / 23 bins at 16 kHz), chain length known at compile time: ONE wait for the last
+        // operand read (they return in order), then nothing but the chain
+        land_quad(mm_x[MMQ - 1]);
+#pragma unroll
+        for (int t = 0; t < MMQ; ++t) SNF_QUAD(mm_w[t], mm_x[t]);
+      } else if (n_quads == 7 || n_quads == 6) {
+        // the same shapes where the plan is not a template parameter (NJ = 16): the reads are placed by the
+        // compiler, which interleaves about half of them with the chain
         float4 a[7], x[7];
 #pragma unroll
         for (int t = 0; t < 7; ++t) {
@@ -408,7 +447,22 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
       const int mm_out = NJ == 13 ? mm_out_once : reinterpret_cast<const int*>(mm_lane)[64];
       // a wide group is split over up to 4 neighbouring blocks of one 16-lane row: the first block adds
       // the sums of the others (0 / 1 factors per lane; one v_fmac_f32 with a DPP row shift each)
-      if (p.mm_levels > 1) {
+      if (LV == 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float own = mel[i];
+          fmac_row_shl<4>(mel[i], own, mm_f[0]);
+          fmac_row_shl<8>(mel[i], own, mm_f[1]);
+          fmac_row_shl<12>(mel[i], own, mm_f[2]);
+        }
+      } else if (LV == 3) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float own = mel[i];
+          fmac_row_shl<4>(mel[i], own, mm_f[0]);
+          fmac_row_shl<8>(mel[i], own, mm_f[1]);
+        }
+      } else if (p.mm_levels > 1) {
         const float mm_f1 = mm_lane[128], mm_f2 = mm_lane[192], mm_f3 = mm_lane[256];
         // (the test for a fourth block outside the loop over the bins: inside, the compiler kept four
         // branches and a dozen register copies between them)
@@ -458,18 +512,40 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
       if (KIND == SNF_KIND_MFCC) {
         // log-mel of frame j back to its (now idle) power tile; DCT-II + lifter on the vector pipe: lane l
         // of a frame's row owns cepstrum l and walks the log-mel 4 bins at a time
-        wave_lds_order();
-        if (mm_out >= 0)
-          *reinterpret_cast<float4*>(const_cast<float*>(mtile) + mm_out) =
-              make_float4(fast_log(floor_eps(mel[0])), fast_log(floor_eps(mel[1])),
-                          fast_log(floor_eps(mel[2])), fast_log(floor_eps(mel[3])));
-        wave_lds_order();
         const float4* __restrict__ dw = t_dd_v + l;
         const float4* __restrict__ dx = reinterpret_cast<const float4*>(ptile);
+        auto write_log_mel = [&]() {
+          wave_lds_order();
+          if (mm_out >= 0)
+            *reinterpret_cast<float4*>(const_cast<float*>(mtile) + mm_out) =
+                make_float4(fast_log(floor_eps(mel[0])), fast_log(floor_eps(mel[1])),
+                            fast_log(floor_eps(mel[2])), fast_log(floor_eps(mel[3])));
+          wave_lds_order();
+        };
         float v = 0.0f;
-        if (p.dd_groups == 6) {
-          // 21-24 mel bins (the reference's default 23): straight-line, the twelve operand reads issued
-          // before the first multiply-add (same products in the same order as the loop below)
+        // 21-24 mel bins (the reference's default 23): straight-line, every operand in registers before the first
+        // multiply-add (same products in the same order as the loop below)
+        if (NJ == 13 && p.dd_groups == 6) {
+          // the six constant DCT rows are requested in front of the logs and the log-mel write (the registers of
+          // the mel operands are free here); only the six log-mel reads stand behind the write.  They are waited
+          // for one by one (the compiler's counted waits between the groups of four multiply-adds: the chain
+          // starts when the first has landed; ONE wait for all six measured 0.6 % slower on MFCC-13)
+          float4 w[6], x[6];
+          issue_quads<6, 16>(dw, w);
+          write_log_mel();
+          issue_quads<6, 1>(dx, x);
+          // (the energy column's logarithm under the wait for the log-mel: the compiler sinks it to the select in
+          // front of the store, behind the DCT.  Six-quad plans only: four of the seven-quad forms spill with it.)
+          if (ENERGY != 0 && MMQ == 6) asm volatile("" : "+v"(log_energy));
+#pragma unroll
+          for (int g4 = 0; g4 < 6; ++g4) {
+            v += w[g4].x * x[g4].x;
+            v += w[g4].y * x[g4].y;
+            v += w[g4].z * x[g4].z;
+            v += w[g4].w * x[g4].w;
+          }
+        } else if (p.dd_groups == 6) {
+          write_log_mel();
           float4 w[6], x[6];
 #pragma unroll
           for (int g4 = 0; g4 < 6; ++g4) {
@@ -484,6 +560,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
             v += w[g4].w * x[g4].w;
           }
         } else {
+          write_log_mel();
 #pragma unroll 2
           for (int g4 = 0; g4 < p.dd_groups; ++g4) {
             const float4 w = dw[g4 * 16], x = dx[g4];
@@ -493,7 +570,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
             v += w.w * x.w;
           }
         }
-        v *= t_lifter[l];
+        v *= NJ == 13 ? lifter_once : t_lifter[l];
         if (l == 0 && p.use_energy) v = log_energy;
         int oc = l;
         if (p.htk_compat) {
@@ -536,13 +613,13 @@ bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b) {
 
 namespace {
 
-template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER>
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV>
 int launch_dither(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
   const size_t lds = static_cast<size_t>((q.table_floats * 4 + 255) & ~255) + kWaves * 4 * kTileBytes;
   const int64_t n_sets = (b.total_frames + 3) / 4;
   int64_t blocks = (n_sets + kWaves - 1) / kWaves;
   if (blocks > 256) blocks = 256;  // one resident workgroup per CU, grid-stride over the frame sets
-  auto kern = fbank512b_kernel<NJ, KIND, ENERGY, BST, DITHER>;
+  auto kern = fbank512b_kernel<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV>;
   if (lds > 64 * 1024)
     SNF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
@@ -552,10 +629,32 @@ int launch_dither(const Fast512Params& q, const BatchArgs& b, float* out, double
   return SNF_OK;
 }
 
+// The mel plan as a compile-time property of the launch (NJ = 13): chain length 7 / 6 quads and 2-3 / 4 blocks per
+// split group are what the bank plans of 18-40 bins at 16 kHz come to (fast512_build); every other plan, and the
+// NJ = 16 forms (no registers for the operands read ahead), run the form that tests both per set.
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER>
+int launch_plan(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
+  if constexpr (NJ == 13 && (BST || !DITHER)) {
+    // (MFCC with an energy column and dither, 7 quads in 4 blocks: spills 4 registers with the operands read ahead)
+    constexpr bool kFits74 = !(KIND == SNF_KIND_MFCC && DITHER && ENERGY != 0);
+    if (q.mm_quads == 7 && q.mm_levels == 4) {
+      if constexpr (kFits74)
+        return launch_dither<NJ, KIND, ENERGY, BST, DITHER, 7, 4>(q, b, out, energy_out, stream);
+      else
+        return launch_dither<NJ, KIND, ENERGY, BST, DITHER, 0, 0>(q, b, out, energy_out, stream);
+    }
+    if (q.mm_quads == 7 && q.mm_levels >= 2)
+      return launch_dither<NJ, KIND, ENERGY, BST, DITHER, 7, 3>(q, b, out, energy_out, stream);
+    if (q.mm_quads == 6 && q.mm_levels == 4)
+      return launch_dither<NJ, KIND, ENERGY, BST, DITHER, 6, 4>(q, b, out, energy_out, stream);
+  }
+  return launch_dither<NJ, KIND, ENERGY, BST, DITHER, 0, 0>(q, b, out, energy_out, stream);
+}
+
 template <int NJ, int KIND, int ENERGY, bool BST>
 int launch_one(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
-  if (q.dither != 0.0f) return launch_dither<NJ, KIND, ENERGY, BST, true>(q, b, out, energy_out, stream);
-  return launch_dither<NJ, KIND, ENERGY, BST, false>(q, b, out, energy_out, stream);
+  if (q.dither != 0.0f) return launch_plan<NJ, KIND, ENERGY, BST, true>(q, b, out, energy_out, stream);
+  return launch_plan<NJ, KIND, ENERGY, BST, false>(q, b, out, energy_out, stream);
 }
 
 template <int NJ, int KIND>
