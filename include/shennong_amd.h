@@ -655,6 +655,16 @@ int snf_debug_fill_lds(uint32_t pattern);
    them stage by stage with the oracle's.  Valid until the next call on the plan. */
 int snf_debug_pitch_scratch(snf_plan* plan, void** down, void** nccf_res, void** pov_nccf,
                             void** states);
+/* Test aid: the tail of a PLP plan on rows the caller chooses, without the mel front end.  Host arrays:
+   `mel` float32 [total_frames, num_bins] linear mel energies, `energy` float64 [total_frames] linear frame
+   energies, `frame_offsets` int64 [n_utts + 1] (starting at 0), `out` float32 [total_frames, num_ceps].  Runs
+   what the product path runs behind the front end - the RASTA filter if the plan's options ask for it, then
+   the PLP tail with the plan's own parameters - on buffers of its own, with the unwarped tables (warp id 0)
+   for every utterance, and records the kernels in the plan's timing slots (snf_plan_kernel_name).
+   `mel_out` (may be NULL): receives the rows the tail read, float32 [total_frames, num_bins] - the RASTA
+   filter's output on a RASTA plan, the input otherwise.  SNF_E_INVALID for a plan of another kind. */
+int snf_debug_plp_tail(snf_plan* plan, const float* mel, const double* energy,
+                       const int64_t* frame_offsets, int64_t n_utts, float* out, float* mel_out);
 /* Duration in milliseconds of the kernels launched by the last run call on this plan, measured
    with HIP events on the stream the kernels were launched on.  `which` selects a kernel slot:
    0 = whole call, 1.. = per-kernel; returns <0 if the slot was not recorded. */

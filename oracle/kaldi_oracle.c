@@ -598,6 +598,39 @@ ORC_API int32_t orc_ndims(const snf_options* o) {
   }
 }
 
+/* The PLP recipe behind the mel energies (reference plp.py:587-626): equal loudness, compression, IDFT to the
+ * autocorrelation, Durbin, LPC -> cepstrum, lifter / scale, energy, HTK order.  `mel` has nb + 2 slots with the
+ * linear mel energies in 1 .. nb; `log_energy` is the frame's double log energy (used with use_energy). */
+static void plp_tail_row(const snf_options* o, const float* eql, const float* idft, const float* lift,
+                         float* mel, float* ac, float* lpc, float* tmp, float* cep, double log_energy,
+                         double log_floor, float* row) {
+  int nb = o->mel.num_bins;
+  for (int b = 0; b < nb; b++) mel[1 + b] *= eql[b];
+  for (int b = 0; b < nb; b++) mel[1 + b] = powf(mel[1 + b], o->compress_factor);
+  mel[0] = mel[1];
+  mel[nb + 1] = mel[nb];
+  for (int i = 0; i <= o->lpc_order; i++) ac[i] = vecvec(idft + (size_t)i * (nb + 2), mel, nb + 2);
+  for (int i = 0; i < o->lpc_order; i++) lpc[i] = 0.0f;
+  double res = (double)compute_lpc(ac, o->lpc_order, lpc, tmp);
+  if (res < DBL_EPSILON) res = DBL_EPSILON; /* plp.py:603: max(., float64 eps) */
+  orc_lpc2cepstrum(o->lpc_order, lpc, cep);
+  for (int c = 1; c < o->num_ceps; c++) row[c] = cep[c - 1];
+  row[0] = (float)res;
+  if (o->cepstral_lifter != 0.0f)
+    for (int c = 0; c < o->num_ceps; c++) row[c] *= lift[c];
+  if (o->cepstral_scale != 1.0f)
+    for (int c = 0; c < o->num_ceps; c++) row[c] *= o->cepstral_scale;
+  if (o->use_energy) {
+    if (o->energy_floor > 0.0f && log_energy < log_floor) log_energy = log_floor;
+    row[0] = (float)log_energy;
+  }
+  if (o->htk_compat) {
+    float e = row[0];
+    for (int c = 0; c < o->num_ceps - 1; c++) row[c] = row[c + 1];
+    row[o->num_ceps - 1] = e;
+  }
+}
+
 ORC_API int orc_compute(const snf_options* o, const int16_t* wave16, int64_t n, float vtln_warp,
                         float* out) {
   const snf_frame_options* fo = &o->frame;
@@ -749,35 +782,47 @@ ORC_API int orc_compute(const snf_options* o, const int16_t* wave16, int64_t n, 
     } else { /* PLP, reference plp.py:548-626 */
       melbanks_compute(&mb, win, mel + 1);
       if (o->rasta) rasta_filter(&rasta, mel + 1, mel + 1, 1);
-      for (int b = 0; b < nb; b++) mel[1 + b] *= eql[b];
-      for (int b = 0; b < nb; b++) mel[1 + b] = powf(mel[1 + b], o->compress_factor);
-      mel[0] = mel[1];
-      mel[nb + 1] = mel[nb];
-      for (int i = 0; i <= o->lpc_order; i++) ac[i] = vecvec(idft + (size_t)i * (nb + 2), mel, nb + 2);
-      for (int i = 0; i < o->lpc_order; i++) lpc[i] = 0.0f;
-      double res = (double)compute_lpc(ac, o->lpc_order, lpc, tmp);
-      if (res < DBL_EPSILON) res = DBL_EPSILON; /* plp.py:603: max(., float64 eps) */
-      orc_lpc2cepstrum(o->lpc_order, lpc, cep);
-      for (int c = 1; c < o->num_ceps; c++) row[c] = cep[c - 1];
-      row[0] = (float)res;
-      if (o->cepstral_lifter != 0.0f)
-        for (int c = 0; c < o->num_ceps; c++) row[c] *= lift[c];
-      if (o->cepstral_scale != 1.0f)
-        for (int c = 0; c < o->num_ceps; c++) row[c] *= o->cepstral_scale;
-      if (o->use_energy) {
-        if (o->energy_floor > 0.0f && log_energy < log_floor) log_energy = log_floor;
-        row[0] = (float)log_energy;
-      }
-      if (o->htk_compat) {
-        float e = row[0];
-        for (int c = 0; c < o->num_ceps - 1; c++) row[c] = row[c + 1];
-        row[o->num_ceps - 1] = e;
-      }
+      plp_tail_row(o, eql, idft, lift, mel, ac, lpc, tmp, cep, log_energy, log_floor, row);
     }
   }
   if (kind == SNF_KIND_PLP && o->rasta) rasta_free(&rasta);
   free(wave); free(wfn); free(win); free(mel); free(ac); free(lpc); free(tmp); free(cep);
   melbanks_free(&mb); free(dct); free(lift); free(eql); free(idft);
+  return 0;
+}
+
+/* The PLP tail alone on chosen rows: `mel` [T, num_bins] linear mel energies (after RASTA, if any: orc_rasta),
+ * `energy` [T] linear frame energies (floored at float64 eps, double log: plp.py:191-193), unwarped banks.
+ * The same plp_tail_row orc_compute runs. */
+ORC_API int orc_plp_tail(const snf_options* o, const float* mel_in, const double* energy, int64_t T,
+                         float* out) {
+  if (o->kind != SNF_KIND_PLP) return orc_fail("orc_plp_tail: not a PLP option record");
+  int nb = o->mel.num_bins, order = o->lpc_order, D = o->num_ceps;
+  if (D <= 0 || D > order + 1) return orc_fail("We must have 0 < num_ceps <= lpc_order+1");
+  if (T <= 0) return 0;
+  melbanks_t mb; memset(&mb, 0, sizeof(mb));
+  int rc = melbanks_init(&mb, &o->mel, &o->frame, 1.0f);
+  if (rc) return rc;
+  float* eql = (float*)malloc(sizeof(float) * (size_t)nb);
+  equal_loudness(&mb, eql);
+  float* idft = (float*)malloc(sizeof(float) * (size_t)(order + 1) * (size_t)(nb + 2));
+  idft_bases(order + 1, nb + 2, idft);
+  float* lift = (float*)malloc(sizeof(float) * (size_t)D);
+  if (o->cepstral_lifter != 0.0f) lifter_coeffs(o->cepstral_lifter, lift, D);
+  float* mel = (float*)malloc(sizeof(float) * (size_t)(nb + 2));
+  float* ac = (float*)malloc(sizeof(float) * (size_t)(order + 1));
+  float* lpc = (float*)malloc(sizeof(float) * (size_t)order);
+  float* tmp = (float*)malloc(sizeof(float) * (size_t)order);
+  float* cep = (float*)malloc(sizeof(float) * (size_t)order);
+  double log_floor = o->energy_floor > 0.0f ? log((double)o->energy_floor) : 0.0;
+  for (int64_t t = 0; t < T; t++) {
+    memcpy(mel + 1, mel_in + t * nb, sizeof(float) * (size_t)nb);
+    double e = energy ? energy[t] : 0.0;
+    double log_energy = log(e > DBL_EPSILON ? e : DBL_EPSILON);
+    plp_tail_row(o, eql, idft, lift, mel, ac, lpc, tmp, cep, log_energy, log_floor, out + t * D);
+  }
+  free(mel); free(ac); free(lpc); free(tmp); free(cep); free(lift); free(idft); free(eql);
+  melbanks_free(&mb);
   return 0;
 }
 

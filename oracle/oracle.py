@@ -55,6 +55,7 @@ def lib():
     L.orc_lpc2cepstrum.argtypes = [i32, pf, pf]
     L.orc_lpc2cepstrum.restype = None
     L.orc_rasta.argtypes = [pf, i64, i32, pf, i32]
+    L.orc_plp_tail.argtypes = [OP, pf, C.POINTER(C.c_double), i64, pf]
     L.orc_ndims.argtypes = [OP]
     L.orc_compute.argtypes = [OP, C.POINTER(C.c_int16), i64, f32, pf]
     L.orc_compute_batch.argtypes = [
@@ -162,6 +163,19 @@ def rasta(mel, do_log=True):
     out = np.zeros_like(mel)
     _check(lib().orc_rasta(
         _fp(mel), mel.shape[0], mel.shape[1], _fp(out), int(do_log)))
+    return out
+
+
+def plp_tail(opts, mel, energy):
+    """The PLP recipe behind the mel energies, in the float32 arithmetic of `compute`: `mel` [T, num_bins] linear
+    mel energies (filtered already, if RASTA is wanted: `rasta`), `energy` [T] float64 linear frame energies
+    -> float32 [T, num_ceps]"""
+    mel = np.ascontiguousarray(mel, dtype=np.float32)
+    energy = np.ascontiguousarray(energy, dtype=np.float64)
+    assert mel.ndim == 2 and mel.shape[1] == opts.mel.num_bins and energy.shape == (mel.shape[0],)
+    out = np.zeros((mel.shape[0], opts.num_ceps), dtype=np.float32)
+    _check(lib().orc_plp_tail(
+        C.byref(opts), _fp(mel), energy.ctypes.data_as(C.POINTER(C.c_double)), mel.shape[0], _fp(out)))
     return out
 
 

@@ -369,14 +369,17 @@ def lpc_to_cepstrum(lpc):
     return cep
 
 
-def rasta(mel, do_log=True):
+def rasta(mel, do_log=True, eps=np.finfo(np.float64).eps):
     """RASTA over the frames of one utterance, [n, bins] -> [n, bins] (reference plp.py:64-146: numerator
     -[-2 .. 2] / 10, denominator [1, -0.94]; the first four frames emit zeros in the log domain - ones after
-    the exponential - and prime the FIR delay line)"""
+    the exponential - and prime the FIR delay line).  `eps` is what the filter adds before the logarithm: the
+    reference adds the eps of the frame's own dtype (plp.py:126), and its frames are float32 - `plp` passes
+    float32 eps, as the C oracle and rasta_kernel do (FLT_EPSILON).  Far above 1e-7 the choice does not show;
+    on a quiet bin it is another function."""
     import scipy.signal
     x = np.asarray(mel, dtype=np.float64)
     if do_log:
-        x = np.log(x + np.finfo(np.float64).eps)
+        x = np.log(x + eps)
     numer = -np.arange(-2, 3) / np.sum(np.arange(-2, 3) ** 2)
     denom = np.array([1.0, -0.94])
     out = np.zeros_like(x)
@@ -420,12 +423,27 @@ def plp(wave, sample_rate=16000, frame_shift=0.01, frame_length=0.025, preemph=0
     w, centers = mel_banks_vtln(num_bins, sample_rate, padded, low_freq, high_freq, vtln_low, vtln_high, warp)
     mel = power @ w.T
     if use_rasta:
-        mel = rasta(mel, do_log=True)
+        # (the reference's frames are float32: its filter adds float32 eps, plp.py:126)
+        mel = rasta(mel, do_log=True, eps=float(np.finfo(np.float32).eps))
+    le = raw_log_energy if raw_energy else post_log_energy
+    return plp_tail(mel, centers, le, lpc_order=lpc_order, num_ceps=num_ceps, cepstral_lifter=cepstral_lifter,
+                    cepstral_scale=cepstral_scale, compress_factor=compress_factor, use_energy=use_energy,
+                    energy_floor=energy_floor, htk_compat=htk_compat)
+
+
+def plp_tail(mel, centers, log_energy, lpc_order=12, num_ceps=13, cepstral_lifter=22.0, cepstral_scale=1.0,
+             compress_factor=1.0 / 3.0, use_energy=True, energy_floor=0.0, htk_compat=False):
+    """The PLP recipe behind the mel energies (reference plp.py:587-626) in float64: `mel` [n, bins] linear mel
+    energies (RASTA-filtered already, if wanted), `centers` [bins] the banks' centre frequencies in Hz,
+    `log_energy` [n] the frames' log energies (read with use_energy only) -> [n, num_ceps]"""
+    mel = np.asarray(mel, dtype=np.float64)
+    num_bins = mel.shape[1]
+    eps64 = np.finfo(np.float64).eps
     mel = (mel * equal_loudness(centers)[None, :]) ** float(np.float32(compress_factor))
     dup = np.concatenate([mel[:, :1], mel, mel[:, -1:]], axis=1)
     ac = dup @ idft_bases(lpc_order + 1, num_bins + 2).T
-    out = np.zeros((x.shape[0], num_ceps))
-    for t in range(x.shape[0]):
+    out = np.zeros((mel.shape[0], num_ceps))
+    for t in range(mel.shape[0]):
         lpc, e = durbin(ac[t])
         out[t, 0] = max(np.log(e), eps64)
         out[t, 1:] = lpc_to_cepstrum(lpc)[:num_ceps - 1]
@@ -433,7 +451,7 @@ def plp(wave, sample_rate=16000, frame_shift=0.01, frame_length=0.025, preemph=0
         out = out * (1 + 0.5 * cepstral_lifter * np.sin(np.pi * np.arange(num_ceps) / cepstral_lifter))[None, :]
     out = out * cepstral_scale
     if use_energy:
-        le = raw_log_energy if raw_energy else post_log_energy
+        le = np.asarray(log_energy, dtype=np.float64)
         if energy_floor > 0:
             le = np.maximum(le, np.log(energy_floor))
         out[:, 0] = le

@@ -34,6 +34,7 @@ EXPORTS = [
     'snf_cmvn_apply_device', 'snf_concat_columns_device', 'snf_count_nonfinite_device', 'snf_set_noise_call',
     'snf_malloc', 'snf_free', 'snf_memcpy_h2d', 'snf_memcpy_d2h', 'snf_memset',
     'snf_host_malloc', 'snf_host_free', 'snf_debug_fill_lds', 'snf_debug_pitch_scratch',
+    'snf_debug_plp_tail',
     'snf_stream_create', 'snf_stream_destroy', 'snf_stream_synchronize', 'snf_memcpy_h2d_async',
     'snf_memcpy_d2h_async', 'snf_comm_unique_id', 'snf_comm_init', 'snf_comm_rank', 'snf_comm_world_size',
     'snf_comm_destroy', 'snf_comm_gatherv', 'snf_comm_allreduce_f64',
@@ -130,6 +131,7 @@ def lib():
         L.snf_host_free.argtypes = [vp]
         L.snf_debug_fill_lds.argtypes = [C.c_uint32]
         L.snf_debug_pitch_scratch.argtypes = [vp] + [C.POINTER(vp)] * 4
+        L.snf_debug_plp_tail.argtypes = [vp, pf, C.POINTER(C.c_double), pi64, i64, pf, pf]
         L.snf_stream_create.argtypes = [C.POINTER(vp)]
         L.snf_stream_destroy.argtypes = [vp]
         L.snf_stream_synchronize.argtypes = [vp]
@@ -322,6 +324,30 @@ class Plan:
     def kernel_name(self, which):
         name = lib().snf_plan_kernel_name(self.handle, which)
         return name.decode() if name else None
+
+    def debug_plp_tail(self, mel, energy, frame_offsets=None, mel_out=False):
+        """Test aid (snf_debug_plp_tail): the tail of a PLP plan on chosen rows.  `mel` float32 [frames, num_bins]
+        linear mel energies, `energy` float64 [frames] linear frame energies, `frame_offsets` the utterance
+        boundaries (default: one utterance) -> float32 [frames, num_ceps]; with `mel_out` also the rows the tail
+        read (the RASTA filter's output on a RASTA plan)"""
+        mel = np.ascontiguousarray(mel, dtype=np.float32)
+        energy = np.ascontiguousarray(energy, dtype=np.float64)
+        nbins = int(self.opts.mel.num_bins)
+        if mel.ndim != 2 or mel.shape[1] != nbins or energy.shape != (mel.shape[0],):
+            raise ValueError('mel must be [frames, num_bins] and energy [frames]')
+        if frame_offsets is None:
+            frame_offsets = [0, mel.shape[0]]
+        foff = np.ascontiguousarray(frame_offsets, dtype=np.int64)
+        if foff.ndim != 1 or foff.shape[0] < 2 or foff[-1] != mel.shape[0]:
+            raise ValueError('frame_offsets must end at the number of rows')
+        out = np.zeros((mel.shape[0], self.ndims), dtype=np.float32)
+        filtered = np.zeros_like(mel) if mel_out else None
+        check(lib().snf_debug_plp_tail(
+            self.handle, mel.ctypes.data_as(C.POINTER(C.c_float)), energy.ctypes.data_as(C.POINTER(C.c_double)),
+            foff.ctypes.data_as(C.POINTER(C.c_int64)), foff.shape[0] - 1,
+            out.ctypes.data_as(C.POINTER(C.c_float)),
+            filtered.ctypes.data_as(C.POINTER(C.c_float)) if mel_out else None))
+        return (out, filtered) if mel_out else out
 
     # -- Audio -> Features --
     def run(self, waves, vtln_warps=None, check_finite=False, wrap=None):

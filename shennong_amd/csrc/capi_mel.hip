@@ -419,8 +419,10 @@ int snf_plan_run_batch_device(snf_plan* plan, const int16_t* d_wave, const int64
       if ((rc = launch_rasta(ms.mel.as<float>(), c.b, nb, s))) return rc;
       c.mark("rasta_kernel");
     }
-    if ((rc = launch_plp_tail(plan->pp, c.b, ms.mel.as<float>(), ms.energy.as<double>(), d_out, s))) return rc;
-    c.mark("plp_tail_kernel");
+    const char* tail_launched = nullptr;
+    if ((rc = launch_plp_tail(plan->pp, c.b, ms.mel.as<float>(), ms.energy.as<double>(), d_out, s, &tail_launched)))
+      return rc;
+    if (tail_launched) c.mark(tail_launched);
   } else {
     // append_deltas as two launches: the cepstra go to a scratch, the delta kernel forms the rows
     float* feat_out = d_out;
@@ -489,6 +491,59 @@ int snf_plan_run_batch(snf_plan* plan, const int16_t* wave, const int64_t* sampl
                                      frame_offsets, nullptr);
   if (rc || total_frames == 0) return rc;
   return download(plan, out, d_out, sizeof(float) * total_frames * plan->ndims);
+}
+
+// Test aid (include/shennong_amd.h): what snf_plan_run_batch_device runs behind the mel front end of a PLP plan -
+// launch_rasta if the options ask for it, launch_plp_tail with the plan's PlpParams - on rows the caller chose.
+// The buffers are the call's own (RASTA filters in place; the plan's scratch and offsets cache stay as they are).
+int snf_debug_plp_tail(snf_plan* plan, const float* mel, const double* energy, const int64_t* frame_offsets,
+                       int64_t n_utts, float* out, float* mel_out) {
+  if (!plan || plan->kind != SNF_KIND_PLP) return set_error(SNF_E_INVALID, "not a PLP plan");
+  if (n_utts < 0) return set_error(SNF_E_INVALID, "n_utts < 0");
+  if (n_utts == 0) return SNF_OK;
+  if (!frame_offsets) return set_error(SNF_E_INVALID, "null offsets table");
+  if (frame_offsets[0] != 0) return set_error(SNF_E_INVALID, "offsets tables must start at 0");
+  for (int64_t u = 0; u < n_utts; ++u)
+    if (frame_offsets[u + 1] < frame_offsets[u])
+      return set_error(SNF_E_INVALID, "offsets tables must be non-decreasing");
+  const int64_t total_frames = frame_offsets[n_utts];
+  if (total_frames == 0) return SNF_OK;
+  if (!mel || !energy || !out) return set_error(SNF_E_INVALID, "null pointer");
+  std::lock_guard<std::mutex> host_lock(plan->host_mu);
+  std::lock_guard<std::mutex> lock(plan->mu);
+  int rc = guard_device(plan);
+  if (rc) return rc;
+  if (!plan->base_banks_error.empty()) return set_error(SNF_E_RUNTIME, plan->base_banks_error);
+  if ((rc = sync_warp_tables(plan))) return rc;
+  hipStream_t s = plan->stream;
+  const size_t nf = static_cast<size_t>(total_frames);
+  const size_t nb = static_cast<size_t>(plan->o.mel.num_bins), nc = static_cast<size_t>(plan->ndims);
+  DevBuf d_mel, d_energy, d_foff, d_out;
+  if ((rc = d_mel.ensure(sizeof(float) * nf * nb))) return rc;
+  if ((rc = d_energy.ensure(sizeof(double) * nf))) return rc;
+  if ((rc = d_out.ensure(sizeof(float) * nf * nc))) return rc;
+  if ((rc = d_foff.upload(std::vector<int64_t>(frame_offsets, frame_offsets + n_utts + 1), s))) return rc;
+  SNF_HIP_CHECK(hipMemcpyAsync(d_mel.p, mel, sizeof(float) * nf * nb, hipMemcpyHostToDevice, s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_energy.p, energy, sizeof(double) * nf, hipMemcpyHostToDevice, s));
+  BatchArgs b{};
+  b.frame_offsets = d_foff.as<int64_t>();
+  b.n_utts = n_utts;
+  b.total_frames = total_frames;
+  begin_timing(plan);
+  if (plan->o.rasta) {
+    if ((rc = launch_rasta(d_mel.as<float>(), b, static_cast<int>(nb), s))) return rc;
+    mark_kernel(plan, "rasta_kernel");
+  }
+  const char* launched = nullptr;
+  rc = launch_plp_tail(plan->pp, b, d_mel.as<float>(), d_energy.as<double>(), d_out.as<float>(), s, &launched);
+  if (!rc && launched) mark_kernel(plan, launched);
+  if (!rc) {
+    SNF_HIP_CHECK(hipMemcpyAsync(out, d_out.p, sizeof(float) * nf * nc, hipMemcpyDeviceToHost, s));
+    if (mel_out) SNF_HIP_CHECK(hipMemcpyAsync(mel_out, d_mel.p, sizeof(float) * nf * nb, hipMemcpyDeviceToHost, s));
+  }
+  // (also after a refusal: the uploads read the caller's arrays, and the buffers are freed on return)
+  SNF_HIP_CHECK(hipStreamSynchronize(s));
+  return rc;
 }
 
 }  // extern "C"

@@ -61,7 +61,12 @@ __global__ void rasta_kernel(float* __restrict__ mel, const BatchArgs b, const i
   int count = 0;
   for (int64_t t = f0; t < f1; ++t, ++count) {
     float* cell = mel + t * nb + bin;
-    const float x = logf(*cell + FLT_EPSILON);
+    // (the reference takes numpy's float32 log of its float32 frame, plp.py:126, and the C oracle glibc's logf: both
+    // correctly rounded in all but a handful of arguments.  The device's logf errs by up to 2 ulp, 2e-6 on a log
+    // energy of 14, which the filter's recursion carries into every later frame: against the float64 statement the
+    // filtered rows were up to 7 times as far off as the oracle's, tests/test_plp_tail_gpu.py.  The double logarithm
+    // rounded once gives the reference's value, as log_pitch_of does below.)
+    const float x = static_cast<float>(log(static_cast<double>(*cell + FLT_EPSILON)));
     double y = 0.0;
     if (count < 4) {
       first[count] = x;
@@ -99,6 +104,13 @@ int launch_rasta(float* mel, const BatchArgs& b, int num_bins, hipStream_t strea
   return SNF_OK;
 }
 
+// x^e as the reference forms it: numpy's float32 power and glibc's powf are correctly rounded in all but a handful
+// of arguments, the device's powf is good to an ulp - and the Durbin recursion behind it amplifies that ulp up to
+// 5e4 times on a spectrum nine decades wide.  The double power rounded once gives the reference's value.
+__device__ __forceinline__ float pow_rounded_once(float x, float e) {
+  return static_cast<float>(pow(static_cast<double>(x), static_cast<double>(e)));
+}
+
 // ------------------------------------------------------------------------------------------------
 // PLP tail: equal loudness -> cube-root compression -> IDFT to autocorrelation -> Durbin ->
 // LPC to cepstrum -> lifter/scale -> energy -> HTK reorder.  One thread per frame
@@ -108,6 +120,10 @@ int launch_rasta(float* mel, const BatchArgs& b, int num_bins, hipStream_t strea
 __global__ void plp_tail_kernel(const PlpParams p, const BatchArgs b,
                                 const float* __restrict__ mel, const double* __restrict__ energy,
                                 float* __restrict__ out) {
+  // The reference's arithmetic, operation by operation (tests/test_plp_tail_gpu.py holds the kernel to the float32
+  // oracle at the parity tolerance on spectra where Durbin amplifies a last-place difference past it): no product
+  // is fused into the sum behind it, here and in plp_tail_small_kernel.
+#pragma clang fp contract(off)
   const int64_t g = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
   if (g >= b.total_frames) return;
   const int nb = p.num_bins, order = p.lpc_order, nc = p.num_ceps;
@@ -117,7 +133,7 @@ __global__ void plp_tail_kernel(const PlpParams p, const BatchArgs b,
   float m[kMaxBins + 2];
   for (int i = 0; i < nb; ++i) {
     float v = mel[g * nb + i] * eql[i];
-    m[i + 1] = powf(v, p.compress_factor);
+    m[i + 1] = pow_rounded_once(v, p.compress_factor);
   }
   m[0] = m[1];
   m[nb + 1] = m[nb];
@@ -179,6 +195,7 @@ __global__ __launch_bounds__(64) void plp_tail_small_kernel(const PlpParams p, c
                                                             const float* __restrict__ mel,
                                                             const double* __restrict__ energy,
                                                             float* __restrict__ out) {
+#pragma clang fp contract(off)
   __shared__ float rows[64 * NBMAX];
   const int nb = p.num_bins, order = p.lpc_order, nc = p.num_ceps;
   const int64_t g0 = static_cast<int64_t>(blockIdx.x) * 64;
@@ -199,7 +216,7 @@ __global__ __launch_bounds__(64) void plp_tail_small_kernel(const PlpParams p, c
     m[i + 1] = 0.0f;
     if (i < nb) {
       const float v = rows[threadIdx.x * nb + i] * eql[i];
-      m[i + 1] = powf(v, p.compress_factor);
+      m[i + 1] = pow_rounded_once(v, p.compress_factor);
     }
   }
   m[0] = m[1];
@@ -306,6 +323,57 @@ __device__ __forceinline__ float pow_third(float x, float e) {
   return x > 0.0f ? y : 0.0f;
 }
 
+// One frame of the tail in the reference's arithmetic with compile-time bounds: plp_tail_kernel's operations in its
+// order (the double power rounded once, products and sums rounded apart, -log(1 / E) and the cepstrum recursion in
+// double), for plp_tail_exact_kernel<.., REF = true>.
+template <int NB, int ORD>
+__device__ __forceinline__ void plp_reference_frame(const float* __restrict__ row, const float* __restrict__ eql,
+                                                    const float* __restrict__ basis, float compress_factor,
+                                                    double* res_out, float* cep) {
+#pragma clang fp contract(off)
+  float m[NB + 2];
+#pragma unroll 1
+  for (int i = 0; i < NB; ++i) m[i + 1] = pow_rounded_once(row[i] * eql[i], compress_factor);
+  m[0] = m[1];
+  m[NB + 1] = m[NB];
+  float ac[ORD + 1], lpc[ORD], tmp[ORD];
+#pragma unroll
+  for (int i = 0; i <= ORD; ++i) {
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NB + 2; ++j) s += basis[i * (NB + 2) + j] * m[j];
+    ac[i] = s;
+  }
+  float E = ac[0];
+#pragma unroll
+  for (int i = 0; i < ORD; ++i) lpc[i] = tmp[i] = cep[i] = 0.0f;
+#pragma unroll
+  for (int i = 0; i < ORD; ++i) {
+    float ki = ac[i + 1];
+#pragma unroll
+    for (int j = 0; j < i; ++j) ki += lpc[j] * ac[i - j];
+    ki = ki / E;
+    float c = 1 - ki * ki;
+    if (c < 1.0e-5f) c = 1.0e-5f;
+    E *= c;
+    tmp[i] = -ki;
+#pragma unroll
+    for (int j = 0; j < i; ++j) tmp[j] = lpc[j] - ki * lpc[i - j - 1];
+#pragma unroll
+    for (int j = 0; j <= i; ++j) lpc[j] = tmp[j];
+  }
+  const float res_f = static_cast<float>(-log(1.0 / static_cast<double>(E)));
+  *res_out = fmax(static_cast<double>(res_f), DBL_EPSILON);
+#pragma unroll
+  for (int i = 0; i < ORD; ++i) {
+    double sum = 0.0;
+#pragma unroll
+    for (int j = 0; j < i; ++j)
+      sum += static_cast<double>(i - j) * static_cast<double>(lpc[j]) * static_cast<double>(cep[i - j - 1]);
+    cep[i] = static_cast<float>(-static_cast<double>(lpc[i]) - sum / static_cast<double>(i + 1));
+  }
+}
+
 // The same arithmetic in the same order once more, for ONE exact shape (the reference's defaults: 23 mel
 // bins, LPC order 12, 13 cepstra; round 4).  plp_tail_small_kernel<32, 16> predicates every loop of the
 // 32 x 16 bound on the run-time sizes: 1.8 x the multiply-adds of the 25 x 13 IDFT, 1.8 x those of the
@@ -313,7 +381,10 @@ __device__ __forceinline__ float pow_third(float x, float e) {
 // (tools/count_isa.py).  Here every bound is a template argument, the IDFT bases, the equal-loudness curve
 // and the lifter are staged in LDS once per 256-frame workgroup and read as 16-byte broadcasts, and the mel
 // rows arrive through the same coalesced LDS staging.
-template <int NB, int ORD, int NC>
+// REF (a compression exponent other than 1/3, where pow_third does not apply and the recipe is worse conditioned):
+// the same staging and stores around the reference's arithmetic, operation by operation as in plp_tail_kernel - the
+// double power rounded once, no fused products, the double logarithms, the cepstrum recursion as written there.
+template <int NB, int ORD, int NC, bool REF>
 __global__ __launch_bounds__(256) void plp_tail_exact_kernel(const PlpParams p, const BatchArgs b,
                                                              const float* __restrict__ mel,
                                                              const double* __restrict__ energy,
@@ -342,58 +413,64 @@ __global__ __launch_bounds__(256) void plp_tail_exact_kernel(const PlpParams p, 
   int warp_id = 0;
   if (b.utt_warp) warp_id = b.utt_warp[find_utt(b.frame_offsets, b.n_utts, g)];
   const float* __restrict__ eql = p.eql + warp_id * NB;
-  float m[NB + 2];
-  if (p.compress_factor == 0.33333334f && !p.exact_pow) {
-#pragma unroll
-    for (int i = 0; i < NB; ++i) m[i + 1] = pow_third(rows[threadIdx.x * kRowPad + i] * eql[i], p.compress_factor);
+  float cep[ORD];
+  double res;
+  if constexpr (REF) {
+    plp_reference_frame<NB, ORD>(rows + threadIdx.x * kRowPad, eql, basis, p.compress_factor, &res, cep);
   } else {
-#pragma unroll 1
-    for (int i = 0; i < NB; ++i) m[i + 1] = powf(rows[threadIdx.x * kRowPad + i] * eql[i], p.compress_factor);
-  }
-  m[0] = m[1];
-  m[NB + 1] = m[NB];
-  float ac[ORD + 1], lpc[ORD], tmp[ORD], cep[ORD];
-#pragma unroll
-  for (int i = 0; i <= ORD; ++i) {
-    float s = 0.0f;
-#pragma unroll
-    for (int j = 0; j < NB + 2; ++j) s += basis[i * (NB + 2) + j] * m[j];
-    ac[i] = s;
-  }
-  float E = ac[0];
-#pragma unroll
-  for (int i = 0; i < ORD; ++i) lpc[i] = tmp[i] = cep[i] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < ORD; ++i) {
-    float ki = ac[i + 1];
-#pragma unroll
-    for (int j = 0; j < i; ++j) ki += lpc[j] * ac[i - j];
-    ki = ki / E;
-    float c = 1 - ki * ki;
-    if (c < 1.0e-5f) c = 1.0e-5f;
-    E *= c;
-    tmp[i] = -ki;
-#pragma unroll
-    for (int j = 0; j < i; ++j) tmp[j] = lpc[j] - ki * lpc[i - j - 1];
-#pragma unroll
-    for (int j = 0; j <= i; ++j) lpc[j] = tmp[j];
-  }
-  // (round 5) The reference forms -log(1 / E) and the frame's log-energy in float64 and rounds them to float32
-  // (plp.py:601-603, :615-620): a float32 logarithm that is good to an ulp gives the same float32 up to its last
-  // bit (1e-7 relative on values of 5-20, the parity tolerance is 1e-4) at a fifth of the instructions of the
-  // double one.  The LPC -> cepstrum recursion keeps the reference's double accumulation (plp.py:149-168) with
-  // the weights (k + 1) c[k] made once per cepstrum and one fused multiply-add per term: 78 double operations
-  // instead of 198 + 12 divisions, the same sums up to the last bit of a double that is rounded to float next.
-  const float res_f = logf(E);
-  const double res = fmax(static_cast<double>(res_f), DBL_EPSILON);
-  double wcep[ORD];
-#pragma unroll
-  for (int i = 0; i < ORD; ++i) {
-    double sum = 0.0;
-#pragma unroll
-    for (int j = 0; j < i; ++j) sum = fma(static_cast<double>(lpc[j]), wcep[i - j - 1], sum);
-    cep[i] = static_cast<float>(-static_cast<double>(lpc[i]) - sum * (1.0 / static_cast<double>(i + 1)));
-    wcep[i] = static_cast<double>(i + 1) * static_cast<double>(cep[i]);
+    float m[NB + 2];
+    if (p.compress_factor == 0.33333334f && !p.exact_pow) {
+  #pragma unroll
+      for (int i = 0; i < NB; ++i) m[i + 1] = pow_third(rows[threadIdx.x * kRowPad + i] * eql[i], p.compress_factor);
+    } else {
+  #pragma unroll 1
+      for (int i = 0; i < NB; ++i) m[i + 1] = powf(rows[threadIdx.x * kRowPad + i] * eql[i], p.compress_factor);
+    }
+    m[0] = m[1];
+    m[NB + 1] = m[NB];
+    float ac[ORD + 1], lpc[ORD], tmp[ORD];
+  #pragma unroll
+    for (int i = 0; i <= ORD; ++i) {
+      float s = 0.0f;
+  #pragma unroll
+      for (int j = 0; j < NB + 2; ++j) s += basis[i * (NB + 2) + j] * m[j];
+      ac[i] = s;
+    }
+    float E = ac[0];
+  #pragma unroll
+    for (int i = 0; i < ORD; ++i) lpc[i] = tmp[i] = cep[i] = 0.0f;
+  #pragma unroll
+    for (int i = 0; i < ORD; ++i) {
+      float ki = ac[i + 1];
+  #pragma unroll
+      for (int j = 0; j < i; ++j) ki += lpc[j] * ac[i - j];
+      ki = ki / E;
+      float c = 1 - ki * ki;
+      if (c < 1.0e-5f) c = 1.0e-5f;
+      E *= c;
+      tmp[i] = -ki;
+  #pragma unroll
+      for (int j = 0; j < i; ++j) tmp[j] = lpc[j] - ki * lpc[i - j - 1];
+  #pragma unroll
+      for (int j = 0; j <= i; ++j) lpc[j] = tmp[j];
+    }
+    // (round 5) The reference forms -log(1 / E) and the frame's log-energy in float64 and rounds them to float32
+    // (plp.py:601-603, :615-620): a float32 logarithm that is good to an ulp gives the same float32 up to its last
+    // bit (1e-7 relative on values of 5-20, the parity tolerance is 1e-4) at a fifth of the instructions of the
+    // double one.  The LPC -> cepstrum recursion keeps the reference's double accumulation (plp.py:149-168) with
+    // the weights (k + 1) c[k] made once per cepstrum and one fused multiply-add per term: 78 double operations
+    // instead of 198 + 12 divisions, the same sums up to the last bit of a double that is rounded to float next.
+    const float res_f = logf(E);
+    res = fmax(static_cast<double>(res_f), DBL_EPSILON);
+    double wcep[ORD];
+  #pragma unroll
+    for (int i = 0; i < ORD; ++i) {
+      double sum = 0.0;
+  #pragma unroll
+      for (int j = 0; j < i; ++j) sum = fma(static_cast<double>(lpc[j]), wcep[i - j - 1], sum);
+      cep[i] = static_cast<float>(-static_cast<double>(lpc[i]) - sum * (1.0 / static_cast<double>(i + 1)));
+      wcep[i] = static_cast<double>(i + 1) * static_cast<double>(cep[i]);
+    }
   }
   // Round 5: the 13 values of a frame used to leave as 13 dword stores per lane, 52 bytes apart from lane to lane
   // - every store instruction touched 52 cache lines, and the kernel took 0.26 ms whatever arithmetic was left in
@@ -411,9 +488,15 @@ __global__ __launch_bounds__(256) void plp_tail_exact_kernel(const PlpParams p, 
     if (c == 0 && p.use_energy) {
       // (linear frame energy from the mel kernel: a float sum widened to double; the floor of the reference's
       // double logarithm, DBL_EPSILON, is a float32 number too)
-      float le = logf(fmaxf(static_cast<float>(energy[g]), 2.220446049250313e-16f));
-      if (p.has_floor && le < p.log_energy_floor) le = p.log_energy_floor;
-      v = le;
+      if constexpr (REF) {
+        double le = log(fmax(energy[g], DBL_EPSILON));
+        if (p.has_floor && le < p.log_energy_floor) le = p.log_energy_floor;
+        v = static_cast<float>(le);
+      } else {
+        float le = logf(fmaxf(static_cast<float>(energy[g]), 2.220446049250313e-16f));
+        if (p.has_floor && le < p.log_energy_floor) le = p.log_energy_floor;
+        v = le;
+      }
     }
     int oc = c;
     if (p.htk_compat) oc = c == 0 ? NC - 1 : c - 1;
@@ -427,17 +510,21 @@ __global__ __launch_bounds__(256) void plp_tail_exact_kernel(const PlpParams p, 
 }
 
 int launch_plp_tail(const PlpParams& p, const BatchArgs& b, const float* mel, const double* energy,
-                    float* out, hipStream_t stream) {
+                    float* out, hipStream_t stream, const char** launched) {
+  if (launched) *launched = nullptr;
   if (b.total_frames <= 0) return SNF_OK;
   if (p.num_bins > kMaxBins || p.lpc_order > kMaxLpc)
     return set_error(SNF_E_RUNTIME, "PLP: num_bins > 126 or lpc_order > 63 not supported");
   const int threads = 64;
   if (p.num_bins == 23 && p.lpc_order == 12 && p.num_ceps == 13 && !getenv("SNF_PLP_GENERIC_TAIL") &&
       !getenv("SNF_PLP_SMALL_TAIL")) {
-    hipLaunchKernelGGL((plp_tail_exact_kernel<23, 12, 13>),
-                       dim3(static_cast<unsigned>((b.total_frames + 255) / 256)), dim3(256), 0, stream, p, b, mel,
-                       energy, out);
+    const dim3 grid(static_cast<unsigned>((b.total_frames + 255) / 256));
+    if (p.compress_factor == 0.33333334f)
+      hipLaunchKernelGGL((plp_tail_exact_kernel<23, 12, 13, false>), grid, dim3(256), 0, stream, p, b, mel, energy, out);
+    else
+      hipLaunchKernelGGL((plp_tail_exact_kernel<23, 12, 13, true>), grid, dim3(256), 0, stream, p, b, mel, energy, out);
     SNF_HIP_CHECK(hipGetLastError());
+    if (launched) *launched = "plp_tail_exact_kernel";
     return SNF_OK;
   }
   if (p.num_bins <= 32 && p.lpc_order <= 16 && !getenv("SNF_PLP_GENERIC_TAIL")) {
@@ -445,12 +532,14 @@ int launch_plp_tail(const PlpParams& p, const BatchArgs& b, const float* mel, co
                        dim3(static_cast<unsigned>((b.total_frames + threads - 1) / threads)),
                        dim3(threads), 0, stream, p, b, mel, energy, out);
     SNF_HIP_CHECK(hipGetLastError());
+    if (launched) *launched = "plp_tail_small_kernel";
     return SNF_OK;
   }
   hipLaunchKernelGGL(plp_tail_kernel,
                      dim3(static_cast<unsigned>((b.total_frames + threads - 1) / threads)),
                      dim3(threads), 0, stream, p, b, mel, energy, out);
   SNF_HIP_CHECK(hipGetLastError());
+  if (launched) *launched = "plp_tail_kernel";
   return SNF_OK;
 }
 

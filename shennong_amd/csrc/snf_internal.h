@@ -196,8 +196,10 @@ struct DeltaParams {
 int launch_mel_features(const MelParams& p, const BatchArgs& b, float* out, int out_cols,
                         double* energy_out, hipStream_t stream);
 int launch_rasta(float* mel, const BatchArgs& b, int num_bins, hipStream_t stream);
+// `launched`: receives the name of the kernel the rows went to (plp_tail_exact_kernel, plp_tail_small_kernel or
+// plp_tail_kernel; nullptr: nothing was launched)
 int launch_plp_tail(const PlpParams& p, const BatchArgs& b, const float* mel, const double* energy,
-                    float* out, hipStream_t stream);
+                    float* out, hipStream_t stream, const char** launched = nullptr);
 // `tile_info`: scratch of 4 (total_frames / 32 + 2) int64 (nullptr: per-element kernels only), rebuilt
 // from the offsets table when `build_info` is set (the caller keeps it while the table stays the same).
 // `launched`: receives the name of the kernel that computes the rows (delta_flat_o2w2_kernel,

@@ -86,12 +86,49 @@ def test_spectrogram(gpu, audio, wave, opts):
     dict(), dict(use_energy=False), dict(raw_energy=False), dict(htk_compat=True),
     dict(rasta=True), dict(rasta=True, snip_edges=False), dict(num_ceps=5),
     dict(cepstral_lifter=0, cepstral_scale=0.9), dict(lpc_order=8, num_ceps=9),
+    # plp_tail_kernel (more than 32 bins, an order above 16) and the powf branch of plp_tail_exact_kernel
+    dict(num_bins=40), dict(lpc_order=20, num_ceps=21), dict(compress_factor=0.5),
 ])
 def test_plp(gpu, audio, wave, opts):
     proc = PlpProcessor(dither=0, **opts)
     got = proc.process(audio)
     want = _oracle(proc, wave)
+    assert _plp_tail_kernel(proc) == _plp_tail_route(proc)
     assert_close(got.data, want, rtol=1e-4, what=str(opts), family='plp')
+
+
+def _plp_tail_kernel(proc):
+    """the kernel the last call of `proc` ran its tail on: the last slot the plan recorded"""
+    plan = _backend.get_plan(proc._build_options())
+    return [n for n in (plan.kernel_name(k) for k in range(1, 7)) if n][-1]
+
+
+def _plp_tail_route(proc):
+    """launch_plp_tail's routing (kernels_post.hip), restated"""
+    if (proc.num_bins, proc.lpc_order, proc.num_ceps) == (23, 12, 13):
+        return 'plp_tail_exact_kernel'
+    return 'plp_tail_small_kernel' if proc.num_bins <= 32 and proc.lpc_order <= 16 else 'plp_tail_kernel'
+
+
+@pytest.mark.parametrize('opts', [dict(), dict(num_ceps=12), dict(num_bins=40)],
+                         ids=['plp_tail_exact_kernel', 'plp_tail_small_kernel', 'plp_tail_kernel'])
+def test_plp_tail_routes_with_the_warps_of_a_batch(gpu, request, opts):
+    """each tail route behind the real front end on a batch with per-utterance VTLN warps: 100 + 90 + 131 frames put
+    a warp boundary inside a 256-frame block (frames 100, 190) and inside a 64-frame block, and the total of 321 is a
+    multiple of neither - plp_tail_exact_kernel's lanes past the last frame look up the warp of frame 320.  Every
+    utterance equals its single-utterance run bit for bit and the oracle at the family tolerance."""
+    frames, warps = (100, 90, 131), (0.85, 1.0, 1.2)
+    waves = [synth.utterances(91 + i, 1, 400 + 160 * (f - 1), 16000)[0] for i, f in enumerate(frames)]
+    proc = PlpProcessor(dither=0, **opts)
+    audios = [Audio(w, 16000) for w in waves]
+    together = proc._process_batch(audios, vtln_warp=list(warps))
+    assert _plp_tail_kernel(proc) == _plp_tail_route(proc) == request.node.callspec.id
+    assert [f.shape[0] for f in together] == list(frames)
+    for a, w, wf, f in zip(audios, waves, warps, together):
+        alone = proc._process_batch([a], vtln_warp=[wf])[0]
+        assert _plp_tail_kernel(proc) == request.node.callspec.id
+        assert np.array_equal(alone.data, f.data), wf
+        assert_close(f.data, _oracle(proc, w, wf), rtol=1e-4, what=f'{opts} warp {wf}', family='plp')
 
 
 @pytest.mark.parametrize('warp', [0.85, 1.0, 1.2])
