@@ -522,6 +522,31 @@ int snf_crepe_conv(int device_id, const float* d_x, int64_t frames, int32_t in_l
 int snf_crepe_forward(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
                       int32_t hop, int32_t center, const int32_t* h_filters, const float* const* h_params,
                       float* d_activation, void* stream);
+/* bfloat16 matrix-core path for convolution blocks 2 to 6, which hold nine tenths of the arithmetic and read ReLU
+ * and batch-normalisation outputs of order 1.  The numerics contract: at the input of such a block every
+ * activation and every kernel weight is rounded to bfloat16 (to nearest, ties to even; a NaN stays a NaN), the
+ * products are accumulated in float32 on the matrix cores (v_mfma_f32_32x32x16_bf16) in one fixed order (chains
+ * of 1024 consecutive k ascending from zero, their results added in ascending order); bias, ReLU, scale and
+ * shift, pool and sigmoid are float32 as in snf_crepe_conv.  Rounding is deterministic, so a producer that
+ * stores bfloat16 and a consumer that rounds float32 in its loader see the same bits.  An element depends on
+ * its frame's samples and on K only.  Element types of activations in memory: */
+#define SNF_TYPE_F32 0
+#define SNF_TYPE_BF16 1
+/* snf_crepe_conv with the kernel given as its packed image (snf_pack_weights_bf16 of d_w[width * c_in x c_out],
+ * 16-byte aligned), d_x of type x_type (16-byte aligned; float32 is rounded on the way in) and d_y of type y_type
+ * (bfloat16: rounded on the way out).  The checks of snf_crepe_conv, and: c_in a multiple of 8, width * c_in at
+ * most 2^20, both types known. */
+int snf_crepe_conv_bf16(int device_id, const void* d_x, int32_t x_type, int64_t frames, int32_t in_len, int32_t c_in,
+                        int32_t width, int32_t stride, int32_t pad_left, int32_t positions, const uint16_t* d_packed,
+                        const float* d_b, const float* d_scale, const float* d_shift, int32_t c_out, int32_t flags,
+                        void* d_y, int32_t y_type, void* stream);
+/* snf_crepe_forward with the kernels of blocks 2 to 6 (h_params[4], [8], [12], [16], [20]) given as packed
+ * bfloat16 images and evaluated as snf_crepe_conv_bf16; the outputs of blocks 2 to 5 are kept as bfloat16.  The
+ * ingest, block 1 (unbounded normalised audio, C_in = 1), the classifier (which decides the argmax), every bias,
+ * scale and shift and d_activation are float32 as there.  h_filters[0..4] must be multiples of 8. */
+int snf_crepe_forward_bf16(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                           int32_t hop, int32_t center, const int32_t* h_filters, const void* const* h_params,
+                           float* d_activation, void* stream);
 /* Decoders over d_activation[total_frames x 360]: per frame the maximum (the confidence) and its first
  * index; `viterbi` != 0: the most likely path of the reference's 360-state model over those indices (float64
  * log domain, first index on ties); the weighted average of cents over bins [c - 4, c + 5) around the chosen

@@ -46,7 +46,8 @@ EXPORTS = [
     'snf_affine_apply_segments', 'snf_vtln_gram_rows', 'snf_dense_layer', 'snf_bottleneck_vad',
     'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward', 'snf_crepe_conv',
     'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot', 'snf_packed_weights_bf16_size',
-    'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16']
+    'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
+    'snf_crepe_forward_bf16']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -182,6 +183,9 @@ def lib():
         L.snf_bottleneck_forward_bf16.argtypes = [i32, vp, pi64, i64, pi32, C.POINTER(vp), vp, vp, vp]
         L.snf_crepe_conv.argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp]
         L.snf_crepe_forward.argtypes = [i32, vp, pi64, i64, i32, i32, pi32, C.POINTER(vp), vp, vp]
+        L.snf_crepe_conv_bf16.argtypes = [i32, vp, i32, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp,
+                                          i32, vp]
+        L.snf_crepe_forward_bf16.argtypes = [i32, vp, pi64, i64, i32, i32, pi32, C.POINTER(vp), vp, vp]
         L.snf_crepe_decode.argtypes = [i32, vp, pi64, i64, i32, vp, vp, vp, vp]
         L.snf_framed_onehot.argtypes = [i32, C.c_double, i32, i32, i32, f32, i64, pi64, pf64, pf64, pi32, pi64, pi64,
                                         pi32, pi64, vp, vp, pf, vp]

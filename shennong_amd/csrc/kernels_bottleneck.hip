@@ -58,8 +58,6 @@ namespace snf {
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kBM = 128, kBN = 128, kBK = 32;
 constexpr int kLdA = 34;    // floats per A row in LDS
 constexpr int kLdB = 160;   // floats per B k-row in LDS
@@ -200,12 +198,7 @@ __global__ void __launch_bounds__(kThreads) bn_dense_kernel(const DenseArgs g, i
 }
 
 // ---- bfloat16 dense layer -------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kQK = 64;     // k tile of the bfloat16 kernel: the weight image pads K to a multiple of it
-constexpr unsigned kXcds = 8;
-constexpr int kQLd = 72;    // bfloat16 per tile row in LDS (144 bytes = 9 slots of 16)
-
+// (k tile kQK, LDS row stride kQLd, fragment types and the rounding bf16_rne / bf16_pack2: snf_internal.h)
 struct DenseBf16Args {
   const float* x;
   const uint16_t* wt;   // packed weights Wt[N][Kp]
@@ -214,17 +207,6 @@ struct DenseBf16Args {
   int64_t M;
   int K, Kp, N, act;
 };
-
-// float32 -> bfloat16 by the hardware's conversion (v_cvt_pk_bf16_f32: to nearest, ties to even, subnormals
-// kept, a NaN stays a NaN); one function for both operands
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint16_t bf16_rne(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
-
-__device__ __forceinline__ uint32_t bf16_pack2(float lo, float hi) {
-  f32x2 v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
 
 // 4 consecutive k of row `row` (< M) of x, zeros outside K.  kVec (K a multiple of 4, x 16-byte aligned): one
 // unconditional 16-byte load from a clamped address and a select, so that no branch separates the loads of a tile

@@ -24,6 +24,22 @@
 //     One chain over all k (as in bn_dense_kernel) was measured first: at the full model's K = 65 536 its
 //     round-off (about sqrt(K) eps times the running sum) was 19.5 times that of float32 numpy on the host.
 //
+// bfloat16 convolution (crepe_conv_bf16_kernel, blocks 2 to 6 under precision 'bfloat16'): the same implicit
+// GEMM on v_mfma_f32_32x32x16_bf16, with the tile of bn_dense_bf16_kernel (kernels_bottleneck.hip: block
+// 128 x 128 x 64, 4 waves of 2 x 2 MFMA tiles, both LDS tiles [row][k] at a row stride of 144 bytes, ds_read_b128
+// fragments, register prefetch of the next k tile, XCD-contiguous workgroup order).
+//   * W is the packed image Wt[N][Kp] of bn_pack_bf16_kernel: a B fragment is 16 contiguous bytes.
+//   * A is the gather above, 8 consecutive k per load.  C_in is a multiple of 8, so s, k, L and K are too and
+//     a fragment lies inside the frame's block as a whole or not at all: one 16-byte load of bfloat16 or two of
+//     float32 from a clamped address, then a select (no branch between the loads of a tile).  The source type is
+//     a template parameter: float32 is rounded in the loader before the LDS write (to nearest, ties to even:
+//     block 2 reading block 1), bfloat16 is copied (blocks 3 to 6, whose producers stored that rounding).
+//   * Summation order, fixed per element: chains of kChainBf = 1024 consecutive k (16 k tiles, 64 MFMA steps
+//     of 16 k each) from a zero accumulator, the chains' results added in ascending order.  At K = 65 536 that is 64 steps per chain and 64 chains, the
+//     two levels in balance; the value depends on the frame's samples and K alone.
+//   * Epilogue as above (bias, ReLU, scale and shift, the pool as one v_max over registers r, r + 1, or the
+//     sigmoid), all float32; the store is float32 or bfloat16 (to nearest, ties to even) by an argument.
+//
 // Ingest (crepe_frames_kernel): one workgroup per frame, int16 samples straight from the resident audio (the
 // 512 zeros on either side of a centred signal are an index test, no padded copy exists); mean and deviation
 // from float64 sums in a fixed order (4 samples per thread ascending, then a binary tree in LDS).
@@ -39,8 +55,6 @@
 namespace snf {
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kBM = 128, kBN = 128, kBK = 32;
 constexpr int kLdA = 34;    // floats per A row in LDS
@@ -214,6 +228,183 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2
   }
 }
 
+// ---- bfloat16 convolution -------------------------------------------------------------------------------
+constexpr int kChainBf = 1024;   // k per chain of the bfloat16 kernel (a multiple of kQK)
+
+struct ConvBf16Args {
+  const void* x;        // float32 or bfloat16 (the template parameter)
+  const uint16_t* wt;   // packed kernel Wt[N][Kp]
+  const float* b;
+  const float* scale;
+  const float* shift;
+  void* y;              // float32 or bfloat16 (y_bf16)
+  int64_t M;
+  int K, Kp, N, T, step, lead, L, flags, y_bf16;
+};
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // 8 bfloat16, 16 bytes
+
+// 8 consecutive k of a row, as the loader keeps them until the LDS write
+template <bool kSrcBf16>
+struct Frag8 {
+  float4 lo, hi;
+  __device__ __forceinline__ u32x4 bits() const {
+    return u32x4{bf16_pack2(lo.x, lo.y), bf16_pack2(lo.z, lo.w), bf16_pack2(hi.x, hi.y), bf16_pack2(hi.z, hi.w)};
+  }
+};
+template <>
+struct Frag8<true> {
+  u32x4 q;
+  __device__ __forceinline__ u32x4 bits() const { return q; }
+};
+
+// k .. k + 7 of the row whose run starts `s` elements into the frame block at `base`, read whole from an address
+// clamped into the block (everything is a multiple of 8); `in`: the run lies inside [0, L) and below K, else
+// the LDS write puts zeros.  The select waits until then, so no branch comes between the loads of a tile.
+template <bool kSrcBf16>
+__device__ __forceinline__ Frag8<kSrcBf16> load_a8(const ConvBf16Args& g, int64_t base, int s, int k, bool* in) {
+  const int p = s + k;
+  *in = k < g.K && p >= 0 && p < g.L;
+  const int64_t at = base + min(max(p, 0), g.L - 8);
+  Frag8<kSrcBf16> f;
+  if constexpr (kSrcBf16) {
+    f.q = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(g.x) + at);
+  } else {
+    const float4* src = reinterpret_cast<const float4*>(static_cast<const float*>(g.x) + at);
+    f.lo = src[0];
+    f.hi = src[1];
+  }
+  return f;
+}
+
+template <bool kSrcBf16>
+__global__ void __launch_bounds__(kThreads, 2) crepe_conv_bf16_kernel(const ConvBf16Args g, int n_tiles_n) {
+  __shared__ __attribute__((aligned(16))) uint16_t As[kBM * kQLd];
+  __shared__ __attribute__((aligned(16))) uint16_t Bs[kBN * kQLd];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
+  // every XCD takes a contiguous run of tiles (bn_dense_bf16_kernel): a bijection of the workgroup ids
+  const unsigned nwg = gridDim.x, xcd = blockIdx.x % kXcds, q = nwg / kXcds, rem = nwg % kXcds;
+  const unsigned id = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + blockIdx.x / kXcds;
+  const int64_t m0 = static_cast<int64_t>(id / n_tiles_n) * kBM;
+  const int n0 = static_cast<int>(id % n_tiles_n) * kBN;
+  // loader coordinates, the same for both operands: tile rows l_r + 32 i, k 8 l_c .. 8 l_c + 7.  Tile rows
+  // beyond M and columns beyond N repeat the last one: the epilogue stores neither.
+  const int l_c = tid & 7, l_r = tid >> 3;
+  int64_t a_base[4];
+  int a_s[4], b_col[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int64_t r = min(m0 + l_r + 32 * i, g.M - 1);
+    const int64_t f = r / g.T;
+    a_base[i] = f * g.L;
+    a_s[i] = static_cast<int>(r - f * g.T) * g.step - g.lead;
+    b_col[i] = min(n0 + l_r + 32 * i, g.N - 1);
+  }
+  f32x16 acc[2][2], sum[2][2];   // the running chain; the chains done so far, added in ascending order
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) sum[a][b][r] = 0.0f;
+  Frag8<kSrcBf16> ra[4];
+  u32x4 rb[4];
+  bool a_in[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ra[i] = load_a8<kSrcBf16>(g, a_base[i], a_s[i], 8 * l_c, &a_in[i]);
+    rb[i] = *reinterpret_cast<const u32x4*>(g.wt + static_cast<int64_t>(b_col[i]) * g.Kp + 8 * l_c);
+  }
+  const uint16_t* pa = As + (wm * 64 + li) * kQLd + 8 * lh;
+  const uint16_t* pb = Bs + (wn * 64 + li) * kQLd + 8 * lh;
+  for (int kc = 0; kc < g.K; kc += kChainBf) {   // one chain: from a zero accumulator, then into the sum
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
+    const int kend = min(kc + kChainBf, g.K);
+    for (int k0 = kc; k0 < kend; k0 += kQK) {
+      __syncthreads();   // the previous tile's operand reads are done
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        *reinterpret_cast<u32x4*>(As + (l_r + 32 * i) * kQLd + 8 * l_c) = a_in[i] ? ra[i].bits() : u32x4{0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4*>(Bs + (l_r + 32 * i) * kQLd + 8 * l_c) = rb[i];
+      }
+      __syncthreads();
+      if (k0 + kQK < g.K) {   // (the image is padded to Kp: the whole tile is there)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          ra[i] = load_a8<kSrcBf16>(g, a_base[i], a_s[i], k0 + kQK + 8 * l_c, &a_in[i]);
+          rb[i] = *reinterpret_cast<const u32x4*>(g.wt + static_cast<int64_t>(b_col[i]) * g.Kp + k0 + kQK + 8 * l_c);
+        }
+      }
+      // always the whole tile: beyond K both operands are zeros in LDS, and a zero product leaves a sum as it is
+#pragma unroll
+      for (int s = 0; s < kQK / 16; ++s) {
+        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(pa + 16 * s);
+        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(pa + 32 * kQLd + 16 * s);
+        const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(pb + 16 * s);
+        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(pb + 32 * kQLd + 16 * s);
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) sum[a][b] += acc[a][b];
+  }
+  // epilogue as crepe_conv_kernel: bias, ReLU and normalisation or sigmoid, the pool over the
+  // row pair, one store per output in the output's type
+  const bool norm = g.flags & kConvNorm, pool = g.flags & kConvPool, sigm = g.flags & kConvSigmoid;
+  float* yf = static_cast<float*>(g.y);
+  uint16_t* yh = static_cast<uint16_t*>(g.y);
+#pragma unroll
+  for (int tn = 0; tn < 2; ++tn) {
+    const int c = n0 + wn * 64 + tn * 32 + li;
+    if (c >= g.N) continue;
+    const float bias = g.b[c];
+    const float sc = norm ? g.scale[c] : 1.0f, sh = norm ? g.shift[c] : 0.0f;
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) {
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) {
+        const int64_t row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;   // even; r + 1 is row + 1
+        float v0 = sum[tm][tn][r] + bias, v1 = sum[tm][tn][r + 1] + bias;
+        if (norm) {
+          v0 = fmaf(fmaxf(v0, 0.0f), sc, sh);
+          v1 = fmaf(fmaxf(v1, 0.0f), sc, sh);
+        }
+        if (sigm) {
+          v0 = crepe_sigmoid(v0);
+          v1 = crepe_sigmoid(v1);
+        }
+        if (pool) {   // (M is even: the pair is inside together)
+          v0 = fmaxf(v0, v1);
+          if (row < g.M) {
+            if (g.y_bf16) yh[(row >> 1) * g.N + c] = bf16_rne(v0);
+            else yf[(row >> 1) * g.N + c] = v0;
+          }
+        } else {
+          if (row < g.M) {
+            if (g.y_bf16) yh[row * g.N + c] = bf16_rne(v0);
+            else yf[row * g.N + c] = v0;
+          }
+          if (row + 1 < g.M) {
+            if (g.y_bf16) yh[(row + 1) * g.N + c] = bf16_rne(v1);
+            else yf[(row + 1) * g.N + c] = v1;
+          }
+        }
+      }
+    }
+  }
+}
+
 // ---- ingest ---------------------------------------------------------------------------------------------
 // frames [first, first + count) of the batch, normalised, to out[count x 1024]
 __global__ void __launch_bounds__(kThreads) crepe_frames_kernel(const int16_t* __restrict__ wave,
@@ -378,6 +569,25 @@ int launch_crepe_conv(const float* x, int64_t frames, int T, int step, int lead,
   if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "crepe: too many tiles for one launch");
   hipLaunchKernelGGL(crepe_conv_kernel, dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g,
                      tiles_n);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+int launch_crepe_conv_bf16(const void* x, int x_bf16, int64_t frames, int T, int step, int lead, int L, int K,
+                           const uint16_t* wt, const float* b, const float* scale, const float* shift, int N,
+                           int flags, void* y, int y_bf16, hipStream_t stream) {
+  if (frames <= 0) return SNF_OK;
+  if (step % 8 || lead % 8 || L % 8 || K % 8 || L < 8 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(wt)) & 15))
+    return set_error(SNF_E_INVALID, "crepe: the bfloat16 convolution needs multiples of 8 channels and 16-byte aligned operands");
+  ConvBf16Args g;
+  g.x = x; g.wt = wt; g.b = b; g.scale = scale; g.shift = shift; g.y = y;
+  g.M = frames * T; g.K = K; g.Kp = bn_bf16_padded_k(K); g.N = N; g.T = T; g.step = step; g.lead = lead; g.L = L;
+  g.flags = flags; g.y_bf16 = y_bf16;
+  const int64_t tiles_m = (g.M + kBM - 1) / kBM;
+  const int tiles_n = (N + kBN - 1) / kBN;
+  if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "crepe: too many tiles for one launch");
+  hipLaunchKernelGGL(x_bf16 ? crepe_conv_bf16_kernel<true> : crepe_conv_bf16_kernel<false>,
+                     dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g, tiles_n);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
 }

@@ -8,6 +8,11 @@ parameters, properties and messages as the reference's processor/pitch_crepe.py 
 here the framing, the network and the decoders are HIP kernels (``kernels_crepe.hip``): the convolutions run
 as implicit GEMMs on the FP32 matrix cores, and ``process_all`` is one batched run over all utterances.
 
+Beyond the reference: the attribute :attr:`CrepePitchProcessor.precision` (``'float32'`` by default) selects a
+bfloat16 matrix-core path for convolution blocks 2 to 6, nine tenths of the arithmetic: their input
+activations and kernels are rounded to bfloat16 (to nearest, ties to even) and the products accumulated in
+float32; the ingest, block 1, the classifier, the decoders and the host tail are the float32 path unchanged.
+
 Weights: the five pretrained models are not shipped with this package.  ``model-<capacity>.npz`` is looked up
 in the directory named by the environment variable ``SHENNONG_AMD_CREPE_DIR`` and then in
 ``shennong_amd/share/crepe/``; ``tools/convert_crepe_h5.py`` writes that file from the published Keras
@@ -49,6 +54,8 @@ _BASE_FILTERS = (32, 4, 4, 4, 8, 16)
 _WIDTHS = (512, 64, 64, 64, 64, 64)
 _FRAME, _BINS, _EPSILON, _BAND = 1024, 360, 1e-3, 11
 _BN = ('gamma', 'beta', 'moving_mean', 'moving_variance')
+PRECISIONS = ('float32', 'bfloat16')
+_PACKED = (4, 8, 12, 16, 20)    # the kernels of blocks 2 to 6 among the 26 parameters: the bfloat16 path's layers
 
 _LOCK = threading.Lock()
 _LOADED = {}    # (capacity, file) -> validated host parameters
@@ -137,6 +144,36 @@ class _DeviceModel:
             self.buffers.append(buf)
         self.pointers = (C.c_void_p * 26)(*[b.ptr for b in self.buffers])
         self.filters = (C.c_int32 * 6)(*filters(capacity))
+        self.shapes = [a.shape for a in params]
+        self.device = device
+        self._packed = None
+
+    def packed_pointers(self):
+        """The 26 pointers with the kernels of blocks 2 to 6 as packed bfloat16 images (built on first use and
+        kept beside the float32 weights)"""
+        with _LOCK:
+            if self._packed is None:
+                pointers = [b.ptr for b in self.buffers]
+                images = []
+                for i in _PACKED:
+                    images.append(pack_weights(self.buffers[i], *self.shapes[i], self.device))
+                    pointers[i] = images[-1].ptr
+                self._packed = (images, (C.c_void_p * 26)(*pointers))
+            return self._packed[1]
+
+
+def _check_precision(value):
+    if value not in PRECISIONS:
+        raise ValueError('invalid precision "{}", choose in "{}"'.format(value, ', '.join(PRECISIONS)))
+    return value
+
+
+def pack_weights(w, k, n, device):
+    """The packed bfloat16 image (a DeviceBuffer) of the float32 matrix [k, n] in the DeviceBuffer `w`"""
+    L = _backend.lib()
+    image = _backend.DeviceBuffer(max(16, 2 * int(L.snf_packed_weights_bf16_size(k, n))), device)
+    _backend.check(L.snf_pack_weights_bf16(device, _p(w), k, n, _p(image), None))
+    return image
 
 
 def device_model(capacity, device, path=None):
@@ -214,12 +251,20 @@ class CrepeBatch:
         self.wave = _backend.upload_rows(waves, np.int16, self.device)
         self.activation = self.out = self.bins = None
 
-    def forward(self, model):
-        """The activation [total_frames, 360] stays on the device"""
+    def forward(self, model, precision='float32'):
+        """The activation [total_frames, 360] float32 stays on the device.  `precision` 'bfloat16': blocks 2 to 6
+        on the bfloat16 matrix cores"""
+        _check_precision(precision)
         self.activation = _backend.DeviceBuffer(max(16, 4 * _BINS * self.total_frames), self.device)
-        _backend.check(_backend.lib().snf_crepe_forward(
-            self.device, _p(self.wave), _off(self.soff), self.n, self.hop, int(self.center), model.filters,
-            model.pointers, _p(self.activation), None))
+        L = _backend.lib()
+        if precision == 'bfloat16':
+            _backend.check(L.snf_crepe_forward_bf16(
+                self.device, _p(self.wave), _off(self.soff), self.n, self.hop, int(self.center), model.filters,
+                model.packed_pointers(), _p(self.activation), None))
+        else:
+            _backend.check(L.snf_crepe_forward(
+                self.device, _p(self.wave), _off(self.soff), self.n, self.hop, int(self.center), model.filters,
+                model.pointers, _p(self.activation), None))
 
     def set_activation(self, activation):
         """Replaces the network's output by a host matrix [total_frames, 360] (the decoder alone)"""
@@ -247,10 +292,28 @@ class CrepeBatch:
         return self.bins.download(np.empty((2, self.total_frames), dtype=np.int32))
 
 
+def _to_bf16_bits(a):
+    """The upper halves of float32 values that bfloat16 holds exactly"""
+    bits = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    if (bits & np.uint32(0xFFFF)).any():
+        raise ValueError('convolution: a bfloat16 source must hold values that bfloat16 represents exactly')
+    return (bits >> np.uint32(16)).astype(np.uint16)
+
+
 def conv_layer(x, kernel, bias, scale=None, shift=None, stride=1, pad_left=31, pool=True, sigmoid=False,
-               device=None):
+               device=None, precision='float32', source='float32', store='float32'):
     """One convolution block on the device through ``snf_crepe_conv``: `x` [frames, length, C_in], `kernel`
-    [width, C_in, C_out]; ReLU and ``* scale + shift`` when `scale` is given, then the pool or the sigmoid"""
+    [width, C_in, C_out]; ReLU and ``* scale + shift`` when `scale` is given, then the pool or the sigmoid.
+
+    With `precision` 'bfloat16' through ``snf_pack_weights_bf16`` and ``snf_crepe_conv_bf16``: `x` and `kernel`
+    rounded to bfloat16 on the device, everything after the products float32.  `source` 'bfloat16' uploads `x`
+    as bfloat16 (its values must be exact in that format), `store` 'bfloat16' has the device round the result
+    to bfloat16 on the way out; float32 host arrays in and out either way."""
+    _check_precision(precision)
+    _check_precision(source)
+    _check_precision(store)
+    if precision == 'float32' and (source, store) != ('float32', 'float32'):
+        raise ValueError('convolution: bfloat16 source and store belong to precision "bfloat16"')
     x = np.ascontiguousarray(x, dtype=np.float32)
     kernel = np.ascontiguousarray(kernel, dtype=np.float32)
     if x.ndim != 3 or kernel.ndim != 3 or kernel.shape[1] != x.shape[2]:
@@ -259,20 +322,28 @@ def conv_layer(x, kernel, bias, scale=None, shift=None, stride=1, pad_left=31, p
     width, _, c_out = kernel.shape
     positions = -(-length // stride)
     flags = (1 if scale is not None else 0) | (2 if pool else 0) | (4 if sigmoid else 0)
+    hosts = [_to_bf16_bits(x) if source == 'bfloat16' else x, kernel, np.ascontiguousarray(bias, dtype=np.float32)]
+    hosts += [np.ascontiguousarray(a, dtype=np.float32) for a in ([scale, shift] if scale is not None else [])]
     device = _backend.get_device() if device is None else int(device)
-    hosts = [x, kernel, bias] + ([scale, shift] if scale is not None else [])
     bufs = []
     for a in hosts:
-        a = np.ascontiguousarray(a, dtype=np.float32)
         bufs.append(_backend.DeviceBuffer(max(16, a.nbytes), device))
         bufs[-1].upload(a)
     rows = positions // 2 if pool else positions
-    y = _backend.DeviceBuffer(max(16, 4 * frames * rows * c_out), device)
-    _backend.check(_backend.lib().snf_crepe_conv(
-        device, _p(bufs[0]), frames, length, c_in, width, stride, pad_left, positions, _p(bufs[1]), _p(bufs[2]),
-        _p(bufs[3]) if scale is not None else None, _p(bufs[4]) if scale is not None else None, c_out, flags,
-        _p(y), None))
-    return y.download(np.empty((frames, rows, c_out), dtype=np.float32))
+    out = np.empty((frames, rows, c_out), dtype=np.uint16 if store == 'bfloat16' else np.float32)
+    y = _backend.DeviceBuffer(max(16, out.nbytes), device)
+    norm = [_p(bufs[3]), _p(bufs[4])] if scale is not None else [None, None]
+    if precision == 'bfloat16':
+        image = pack_weights(bufs[1], width * c_in, c_out, device)
+        _backend.check(_backend.lib().snf_crepe_conv_bf16(
+            device, _p(bufs[0]), PRECISIONS.index(source), frames, length, c_in, width, stride, pad_left, positions,
+            _p(image), _p(bufs[2]), *norm, c_out, flags, _p(y), PRECISIONS.index(store), None))
+    else:
+        _backend.check(_backend.lib().snf_crepe_conv(
+            device, _p(bufs[0]), frames, length, c_in, width, stride, pad_left, positions, _p(bufs[1]), _p(bufs[2]),
+            *norm, c_out, flags, _p(y), None))
+    y.download(out)
+    return (out.astype(np.uint32) << np.uint32(16)).view(np.float32) if store == 'bfloat16' else out
 
 
 class CrepePitchProcessor(FeaturesProcessor):
@@ -280,10 +351,14 @@ class CrepePitchProcessor(FeaturesProcessor):
 
     This processor uses the pre-trained CREPE model. The output will have as many rows as there are frames,
     and two columns corresponding to (POV, pitch). POV is the Probability of Voicing.
+
+    Beyond the reference, the attribute :attr:`precision` (not a constructor parameter) selects how convolution
+    blocks 2 to 6 are computed.
     """
     def __init__(self, model_capacity='full', viterbi=True, center=True,
                  frame_shift=0.01, frame_length=0.025):
         super().__init__()
+        self._precision = 'float32'
         self.model_capacity = model_capacity
         self.viterbi = viterbi
         self.center = center
@@ -344,6 +419,23 @@ class CrepePitchProcessor(FeaturesProcessor):
         self._frame_length = value
 
     @property
+    def precision(self):
+        """'float32' (default) or 'bfloat16': with 'bfloat16' convolution blocks 2 to 6 round their input
+        activations and kernels to bfloat16 and run on the bfloat16 matrix cores (float32 accumulation, bias,
+        ReLU, normalisation and pool); the activation differs from the float32 one by about 2e-3"""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        self._precision = _check_precision(value)
+
+    def get_properties(self, **kwargs):
+        """The processor's properties; they record the precision when it is not the default"""
+        if self._precision != 'float32':
+            kwargs.setdefault('precision', self._precision)
+        return super().get_properties(**kwargs)
+
+    @property
     def sample_rate(self):
         """CREPE operates at 16kHz"""
         return 16000
@@ -392,7 +484,7 @@ class CrepePitchProcessor(FeaturesProcessor):
         device = _backend.get_device()
         model = device_model(self.model_capacity, device)
         batch = CrepeBatch(waves, hop, self.center, device)
-        batch.forward(model)
+        batch.forward(model, self._precision)
         raw = batch.decode(self.viterbi)
         properties = self.get_properties()
         feats = []

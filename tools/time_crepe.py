@@ -3,9 +3,12 @@
 synthetic weights (tests/crepe_f64.py).  Host to host, best of 3, every call waits for its stream: the network
 alone (snf_crepe_forward, with the achieved TFLOP/s from the layers' arithmetic), the decoders alone
 (snf_crepe_decode), and process_all.  The float64 numpy statement is timed on the host's CPUs for a few
-utterances and scaled to the batch.  One JSON line per capacity (profiles/crepe_timing.jsonl).
+utterances and scaled to the batch (--host-utts 0 leaves it out).  One JSON line per capacity and precision
+(profiles/crepe_timing.jsonl; profiles/crepe_bf16_timing.jsonl for --precision float32 bfloat16: both in one
+process on the same inputs, each after its own warm-up, the later lines with their gain over float32).
 
     python tools/time_crepe.py [--utts 100] [--seconds 3] [--capacities tiny,full] [--host-utts 1]
+                               [--precision float32 [bfloat16]]
 """
 
 import argparse
@@ -46,6 +49,7 @@ def main():
     ap.add_argument('--seconds', type=float, default=3.0)
     ap.add_argument('--capacities', default='tiny,full')
     ap.add_argument('--host-utts', type=int, default=1)
+    ap.add_argument('--precision', nargs='+', default=['float32'], choices=['float32', 'bfloat16'])
     args = ap.parse_args()
 
     import crepe_f64 as f64
@@ -65,29 +69,41 @@ def main():
             proc = CrepePitchProcessor(model_capacity=capacity)
             model = pitch_crepe.device_model(capacity, _backend.get_device())
             batch = pitch_crepe.CrepeBatch(waves, 160, True)
-            batch.forward(model)     # warm-up: code objects, scratch
-            batch.decode(True)
-            proc.process_all(utterances)
-            forward = best_of(3, lambda: batch.forward(model))
-            decode_viterbi = best_of(3, lambda: batch.decode(True))
-            decode_plain = best_of(3, lambda: batch.decode(False))
-            whole = best_of(3, lambda: proc.process_all(utterances))
             flop = 2.0 * macs_per_frame(pitch_crepe.filters(capacity)) * batch.total_frames
-            rounded = {k: v.astype(np.float32).astype(np.float64) for k, v in weights.items()}
-            t0 = time.perf_counter()
-            for w in waves[:args.host_utts]:
-                f64.process(w, rounded)
-            host = (time.perf_counter() - t0) * args.utts / args.host_utts
-            print(json.dumps({
-                'what': 'crepe', 'capacity': capacity, 'device': _backend.device_name(), 'utts': args.utts,
-                'seconds_each': args.seconds, 'frames': batch.total_frames,
-                'gmac_per_frame': round(macs_per_frame(pitch_crepe.filters(capacity)) / 1e9, 4),
-                'forward_s': round(forward, 5), 'forward_tflops': round(flop / forward / 1e12, 2),
-                'decode_viterbi_s': round(decode_viterbi, 5), 'decode_argmax_s': round(decode_plain, 5),
-                'process_all_s': round(whole, 5),
-                'host_f64_numpy_s_scaled': round(host, 2), 'host_utts_timed': args.host_utts,
-                'host_cpus': len(os.sched_getaffinity(0)),
-                'ratio_host_over_process_all': round(host / whole, 1)}), flush=True)
+            host = None
+            if args.host_utts > 0:
+                rounded = {k: v.astype(np.float32).astype(np.float64) for k, v in weights.items()}
+                t0 = time.perf_counter()
+                for w in waves[:args.host_utts]:
+                    f64.process(w, rounded)
+                host = (time.perf_counter() - t0) * args.utts / args.host_utts
+            plain = None
+            for precision in args.precision:
+                proc.precision = precision
+                batch.forward(model, precision)     # warm-up: code objects, scratch, the packed images
+                batch.decode(True)
+                proc.process_all(utterances)
+                forward = best_of(3, lambda: batch.forward(model, precision))
+                decode_viterbi = best_of(3, lambda: batch.decode(True))
+                decode_plain = best_of(3, lambda: batch.decode(False))
+                whole = best_of(3, lambda: proc.process_all(utterances))
+                line = {
+                    'what': 'crepe', 'capacity': capacity, 'precision': precision, 'device': _backend.device_name(),
+                    'utts': args.utts, 'seconds_each': args.seconds, 'frames': batch.total_frames,
+                    'gmac_per_frame': round(macs_per_frame(pitch_crepe.filters(capacity)) / 1e9, 4),
+                    'forward_s': round(forward, 5), 'forward_tflops': round(flop / forward / 1e12, 2),
+                    'decode_viterbi_s': round(decode_viterbi, 5), 'decode_argmax_s': round(decode_plain, 5),
+                    'process_all_s': round(whole, 5)}
+                if precision == 'float32':
+                    plain = (forward, whole)
+                elif plain is not None:
+                    line['forward_gain_over_float32'] = round(plain[0] / forward, 3)
+                    line['process_all_gain_over_float32'] = round(plain[1] / whole, 3)
+                if host is not None:
+                    line.update({'host_f64_numpy_s_scaled': round(host, 2), 'host_utts_timed': args.host_utts,
+                                 'host_cpus': len(os.sched_getaffinity(0)),
+                                 'ratio_host_over_process_all': round(host / whole, 1)})
+                print(json.dumps(line), flush=True)
 
 
 if __name__ == '__main__':
