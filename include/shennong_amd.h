@@ -581,6 +581,31 @@ int snf_framed_onehot(int device_id, double sample_rate, int32_t frame_length, i
                       const int32_t* h_num_tokens, const int64_t* h_row_offsets, int32_t* d_winners,
                       uint8_t* d_onehot, float* kernel_ms, void* stream);
 
+/* ---- waveform resampling (Kaldi ResampleWaveform, resample.cc; torchaudio kaldi.resample_waveform) ----
+ * An extension: the reference resamples on the host (audio.py:358-424, sox or scipy's Fourier method), one
+ * utterance at a time.  This is Kaldi's LinearResample as ResampleWaveform configures it - a Hann-windowed sinc
+ * with a cutoff of (float)(0.99 * 0.5 * min(rate_in, rate_out)) Hz and 6 zero crossings, the whole signal in one
+ * call (flush) - for a batch that stays on the device.  Rates in [1, 2^22] Hz.
+ */
+/* Output samples of n_in input samples (LinearResample::GetNumOutputSamples with flush = true): the number of
+ * multiples of 1 / rate_out in [0, n_in / rate_in).  Host only.  < 0: SNF_E_INVALID (rates or n_in out of
+ * range). */
+int64_t snf_resample_num_out(int32_t rate_in, int32_t rate_out, int64_t n_in);
+/* Resamples utterance u, the samples [h_src_offsets[u], h_src_offsets[u + 1]) of d_src, into the
+ * snf_resample_num_out samples of d_dst that start at h_dst_starts[u] (any order; the ranges must not overlap,
+ * which is the caller's to ensure).  `kind` 0: int16 in and out, the float32 sum rounded to nearest (ties to even)
+ * and clamped to [-32768, 32767]; 1: float32 in and out.  Every output is one fused multiply-add chain over its
+ * taps ascending from zero (ResampleWaveform hands that sum to BLAS; see the arithmetic contract of the pitch
+ * tracker), so an utterance gives the same bits alone and in any batch.  Offsets tables are HOST int64, buffers
+ * are on the device.  Equal rates, and a rate pair whose phase table (rate_out / gcd rows) and staged input span
+ * do not fit in the 64 KiB of LDS of a workgroup - 44 100 -> 16 001 Hz has 16 001 phases - are SNF_E_INVALID,
+ * found before any device work; n_utts == 0 and empty utterances are fine.  The phase table is built once per
+ * rate pair and kept on the device.  `stream` NULL: the calling thread's own stream; the call waits for its
+ * stream before returning. */
+int snf_linear_resample(int device_id, int32_t rate_in, int32_t rate_out, int32_t kind, const void* d_src,
+                        const int64_t* h_src_offsets, int64_t n_utts, void* d_dst, const int64_t* h_dst_starts,
+                        void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

@@ -47,7 +47,7 @@ EXPORTS = [
     'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward', 'snf_crepe_conv',
     'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot', 'snf_packed_weights_bf16_size',
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
-    'snf_crepe_forward_bf16']
+    'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -189,6 +189,9 @@ def lib():
         L.snf_crepe_decode.argtypes = [i32, vp, pi64, i64, i32, vp, vp, vp, vp]
         L.snf_framed_onehot.argtypes = [i32, C.c_double, i32, i32, i32, f32, i64, pi64, pf64, pf64, pi32, pi64, pi64,
                                         pi32, pi64, vp, vp, pf, vp]
+        L.snf_resample_num_out.argtypes = [i32, i32, i64]
+        L.snf_resample_num_out.restype = i64
+        L.snf_linear_resample.argtypes = [i32, i32, i32, i32, vp, pi64, i64, vp, pi64, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)
@@ -276,6 +279,100 @@ def pitch_num_frames(pitch_opts, nsamples):
 
 
 # ---- plans -------------------------------------------------------------------
+# ---- waveform resampling (snf_linear_resample) --------------------------------
+RESAMPLE_KINDS = {np.dtype(np.int16): 0, np.dtype(np.float32): 1}
+RESAMPLE_CHUNK = 256      # outputs filtered from one staged span (csrc/snf_internal.h kResampleChunk)
+RESAMPLE_RUN = 4 * 256    # consecutive outputs of one workgroup (kResampleChunk * kResampleChunks)
+RESAMPLERS = ('scipy', 'kaldi')   # the `resample` attribute of the processors that work at one rate
+
+
+def check_resampler(value):
+    if value not in RESAMPLERS:
+        raise ValueError('invalid resample "{}", choose in "{}"'.format(value, ', '.join(RESAMPLERS)))
+    return value
+
+
+def resample_num_out(rate_in, rate_out, nsamples):
+    """Samples that `nsamples` at `rate_in` give at `rate_out` (Kaldi's GetNumOutputSamples, whole signal)"""
+    n = int(lib().snf_resample_num_out(int(rate_in), int(rate_out), int(nsamples)))
+    if n < 0:
+        check(n)
+    return n
+
+
+def resample_device(block, soff, rate_in, rate_out, kind, dst=None, dst_starts=None):
+    """Kaldi's ResampleWaveform on a batch that is on the device: utterance u is the samples
+    ``soff[u]:soff[u + 1]`` of the DeviceBuffer `block` (`kind` 0: int16, 1: float32).  The results go to `dst`
+    from sample ``dst_starts[u]`` on (a new buffer holding them end to end when `dst` is None).  Returns
+    ``(dst, out_soff)``, `out_soff` the offsets table of the resampled lengths laid end to end."""
+    soff = np.ascontiguousarray(soff, dtype=np.int64)
+    n = soff.shape[0] - 1
+    if kind not in (0, 1):
+        raise ValueError(f'resample: kind must be 0 (int16) or 1 (float32), it is {kind}')
+    out_soff = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([resample_num_out(rate_in, rate_out, b - a) for a, b in zip(soff[:-1], soff[1:])], out=out_soff[1:])
+    itemsize = 2 if kind == 0 else 4
+    if dst is None:
+        if dst_starts is not None:
+            raise ValueError('resample: dst_starts without dst')
+        dst = DeviceBuffer(max(16, int(out_soff[-1]) * itemsize), block.device)
+        dst_starts = out_soff[:-1]
+    elif dst_starts is None:
+        dst_starts = out_soff[:-1]
+    dst_starts = np.ascontiguousarray(dst_starts, dtype=np.int64)
+    if dst_starts.shape != (n,):
+        raise ValueError(f'resample: {n} utterances, {dst_starts.shape[0]} destination starts')
+    ends = dst_starts + np.diff(out_soff)
+    if n and (dst_starts.min() < 0 or int(ends.max()) * itemsize > dst.nbytes):
+        raise ValueError('resample: a destination range lies outside the destination buffer')
+    if n and int(soff[-1]) * itemsize > block.nbytes:
+        raise ValueError('resample: the offsets table reaches past the source buffer')
+    pi64 = C.POINTER(C.c_int64)
+    check(lib().snf_linear_resample(
+        block.device, int(rate_in), int(rate_out), int(kind), C.c_void_p(block.ptr), soff.ctypes.data_as(pi64), n,
+        C.c_void_p(dst.ptr), dst_starts.ctypes.data_as(pi64), None))
+    return dst, out_soff
+
+
+def native_lengths(waves, rates, native_rate):
+    """Samples of every wave once it is at `native_rate` (its own length when it already is)"""
+    return np.array([w.shape[0] if r == native_rate else resample_num_out(r, native_rate, w.shape[0])
+                     for w, r in zip(waves, rates)], dtype=np.int64)
+
+
+def upload_resampled(waves, rates, native_rate, lengths, device=None):
+    """One int16 block at `native_rate` from int16 `waves` at their own `rates`, in utterance order: the waves
+    of every other rate go up together at that rate and are resampled on the device straight into their
+    slots (`lengths`: :func:`native_lengths`), runs of native-rate waves are copied into theirs.  Nothing is
+    uploaded twice and nothing comes back.  Returns ``(block, soff)``."""
+    device = _DEVICE if device is None else int(device)
+    n = len(waves)
+    soff = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(lengths, out=soff[1:])
+    if all(r == native_rate for r in rates):
+        return upload_rows(waves, np.int16, device), soff
+    block = DeviceBuffer(max(16, 2 * int(soff[-1])), device)
+    i = 0
+    while i < n:
+        j = i
+        while j < n and rates[j] == native_rate:
+            j += 1
+        if j > i and soff[j] > soff[i]:
+            host = np.ascontiguousarray(np.concatenate(waves[i:j]) if j - i > 1 else waves[i], dtype=np.int16)
+            check(lib().snf_memcpy_h2d(C.c_void_p(block.ptr + 2 * int(soff[i])), host.ctypes.data_as(C.c_void_p),
+                                       host.nbytes))
+        i = j + 1
+    for rate in sorted(set(rates) - {native_rate}):
+        members = [k for k in range(n) if rates[k] == rate]
+        group = [waves[k] for k in members]
+        source = upload_rows(group, np.int16, device)
+        goff = np.zeros(len(group) + 1, dtype=np.int64)
+        np.cumsum([w.shape[0] for w in group], out=goff[1:])
+        resample_device(source, goff, rate, native_rate, 0, dst=block, dst_starts=soff[members])
+        source.free()
+    return block, soff
+
+
 class Plan:
     """An immutable device-resident feature plan (window, mel banks, DCT... in HBM)"""
     def __init__(self, opts, device=None, quiet=False):

@@ -8,6 +8,13 @@ the reference falls back to pydub / ffmpeg and to sox for flac, mp3, ...: neithe
 those formats raise a ValueError that says so).  `save` writes WAV files and `resample` is the
 reference's scipy backend (Fourier-domain resampling; its sox backend needs the external binary) -
 neither is on the features path, both are what the reference's callers use (pipeline_manager.py:240).
+
+An extension: ``resample(rate, backend='kaldi')`` is Kaldi's ResampleWaveform (a windowed sinc with a cutoff
+of 0.99 x half the lower rate and 6 zero crossings, torchaudio's ``kaldi.resample_waveform``) as a HIP kernel
+(``kernels_resample.hip``), for mono int16 and float32 signals.  Its output has Kaldi's length - 22 713
+samples at 16 kHz give 11 357 at 8 kHz where the Fourier method gives 11 356 - and its own values; the
+default backend and its results are unchanged.  For one signal it buys nothing over the host; the bottleneck
+and CREPE processors use the same kernel on whole batches that stay on the device.
 """
 
 import collections
@@ -165,16 +172,33 @@ class Audio:
     def resample(self, sample_rate, backend='scipy'):
         """The signal resampled to `sample_rate`, in its own sample type (reference audio.py:358-424).
         `backend` 'scipy' is scipy.signal.resample (Fourier method: exact for band-limited signals, slow
-        for long ones); 'sox' - the reference's default - needs the sox binary and is refused here."""
-        if backend not in ('sox', 'scipy'):
+        for long ones); 'sox' - the reference's default - needs the sox binary and is refused here.
+
+        'kaldi' is this package's extension: Kaldi's ResampleWaveform on the device (cutoff 0.99 x half the
+        lower rate, 6 zero crossings), for mono int16 or float32 signals; int16 results are rounded to
+        nearest and clipped like the scipy backend's.  A signal of n samples gives the multiples of
+        1 / `sample_rate` in [0, n / rate) - one more sample than the scipy backend for some lengths."""
+        if backend not in ('sox', 'scipy', 'kaldi'):
             raise ValueError(f'backend must be sox or scipy, it is {backend}')
         if backend == 'sox':
             raise ValueError('the sox backend needs the sox binary, which is not available here: '
                              'use backend="scipy"')
         if not isinstance(sample_rate, (int, np.integer)) or sample_rate <= 0:
             raise ValueError(f'resampling at {sample_rate} failed!')
+        if backend == 'kaldi':
+            if self.nchannels != 1 or self.dtype not in (np.dtype(np.int16), np.dtype(np.float32)):
+                raise ValueError(f'the kaldi backend resamples mono int16 or float32 signals, this one has '
+                                 f'{self.nchannels} channel(s) of {self.dtype}: use backend="scipy"')
         if sample_rate == self.sample_rate:
             return self
+        if backend == 'kaldi':
+            from shennong_amd import _backend
+            kind = _backend.RESAMPLE_KINDS[self.dtype]
+            source = _backend.upload_rows([np.ascontiguousarray(self.data).reshape(-1)], self.dtype)
+            soff = np.array([0, self.nsamples], dtype=np.int64)
+            block, out_soff = _backend.resample_device(source, soff, self.sample_rate, int(sample_rate), kind)
+            data = block.download(np.empty(int(out_soff[-1]), dtype=self.dtype))
+            return Audio(data, int(sample_rate), validate=False)
         import scipy.signal
         nsamples = int(self.nsamples * sample_rate / self.sample_rate)
         data = scipy.signal.resample(self.data, nsamples)

@@ -271,8 +271,8 @@ static float lowpass_filter(float t, float cutoff, int num_zeros) {
   return filter * window;
 }
 
-void make_linear_resample(int rate_in, int rate_out, float cutoff, int num_zeros,
-                          LinearResampleHost* r) {
+void make_linear_resample_geometry(int rate_in, int rate_out, float cutoff, int num_zeros,
+                                   LinearResampleHost* r) {
   r->rate_in = rate_in;
   r->rate_out = rate_out;
   r->cutoff = cutoff;
@@ -282,8 +282,8 @@ void make_linear_resample(int rate_in, int rate_out, float cutoff, int num_zeros
   r->out_unit = rate_out / base;
   r->first.assign(r->out_unit, 0);
   r->ntaps.assign(r->out_unit, 0);
+  r->weights.clear();
   const double half_width = num_zeros / (2.0 * cutoff);
-  std::vector<std::vector<float>> rows(r->out_unit);
   r->max_taps = 0;
   for (int i = 0; i < r->out_unit; ++i) {
     const double t_out = i / static_cast<double>(rate_out);
@@ -291,17 +291,22 @@ void make_linear_resample(int rate_in, int rate_out, float cutoff, int num_zeros
     const int hi = static_cast<int>(std::floor((t_out + half_width) * rate_in));
     r->first[i] = lo;
     r->ntaps[i] = hi - lo + 1;
-    rows[i].resize(r->ntaps[i]);
-    for (int j = 0; j < r->ntaps[i]; ++j) {
-      const double dt = (lo + j) / static_cast<double>(rate_in) - t_out;
-      rows[i][j] = lowpass_filter(static_cast<float>(dt), cutoff, num_zeros) / rate_in;
-    }
     if (r->ntaps[i] > r->max_taps) r->max_taps = r->ntaps[i];
   }
+}
+
+void make_linear_resample(int rate_in, int rate_out, float cutoff, int num_zeros,
+                          LinearResampleHost* r) {
+  make_linear_resample_geometry(rate_in, rate_out, cutoff, num_zeros, r);
   r->weights.assign(static_cast<size_t>(r->out_unit) * r->max_taps, 0.0f);
-  for (int i = 0; i < r->out_unit; ++i)
-    std::memcpy(r->weights.data() + static_cast<size_t>(i) * r->max_taps, rows[i].data(),
-                sizeof(float) * rows[i].size());
+  for (int i = 0; i < r->out_unit; ++i) {
+    const double t_out = i / static_cast<double>(rate_out);
+    float* row = r->weights.data() + static_cast<size_t>(i) * r->max_taps;
+    for (int j = 0; j < r->ntaps[i]; ++j) {
+      const double dt = (r->first[i] + j) / static_cast<double>(rate_in) - t_out;
+      row[j] = lowpass_filter(static_cast<float>(dt), cutoff, num_zeros) / rate_in;
+    }
+  }
 }
 
 int64_t LinearResampleHost::num_output(int64_t n_in, bool flush) const {

@@ -68,6 +68,9 @@ struct LinearResampleHost {
 };
 void make_linear_resample(int rate_in, int rate_out, float cutoff, int num_zeros,
                           LinearResampleHost* out);
+// ... everything but the weights: the phases' first taps and tap counts (what a size check needs)
+void make_linear_resample_geometry(int rate_in, int rate_out, float cutoff, int num_zeros,
+                                   LinearResampleHost* out);
 
 struct PitchTablesHost {
   int first_lag = 0, last_lag = 0, num_lags = 0, num_states = 0;
@@ -467,6 +470,29 @@ struct OneHotBatch {
   uint8_t* rows;                                              // [total_bytes]
 };
 int launch_framed_onehot(const OneHotBatch& batch, hipStream_t stream);
+
+// General LinearResample (kernels_resample.hip): see that file's header for the design.  The table blob the
+// kernel copies into LDS word for word: first[out_unit] | ntaps[out_unit] | weights[out_unit][stride] (int32,
+// int32, float32); `stride` is max_taps made odd, so that the lanes of a wave, each on its own phase, read
+// different banks.
+constexpr int kResampleChunk = 256;    // outputs a workgroup filters from one staged span
+constexpr int kResampleChunks = 4;     // consecutive chunks per workgroup (its run: 1024 outputs)
+constexpr int kResampleLdsBytes = 64 * 1024;
+struct ResampleTable {
+  int in_unit, out_unit, max_taps, stride;
+  int table_words;   // 32-bit words of the blob
+  int span;          // most input samples any chunk touches: the staged floats
+  const int32_t* blob;   // device
+};
+struct ResampleUtt {   // per utterance, in samples of the element type
+  int64_t src, n_in, dst, n_out;
+};
+// the blob's layout and the span from a table's geometry (`t->blob` stays null); weights may be empty
+void resample_layout(const LinearResampleHost& r, ResampleTable* t);
+void resample_blob(const LinearResampleHost& r, const ResampleTable& t, std::vector<int32_t>* blob);
+// `kind` 0: int16 in and out (rintf, clamped), 1: float32; `d_utts[n_utts]` on the device
+int launch_linear_resample(const ResampleTable& t, int kind, const void* src, const ResampleUtt* d_utts,
+                           int64_t n_utts, int64_t max_out, void* dst, hipStream_t stream);
 
 }  // namespace snf
 

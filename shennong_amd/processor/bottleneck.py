@@ -15,6 +15,13 @@ a bfloat16 matrix-core path for the four layers that read sigmoid outputs (``W2`
 their activations and weights are rounded to bfloat16 (to nearest, ties to even) at the layer's input and the
 products accumulated in float32; everything else is the float32 path unchanged.
 
+Also beyond the reference: the attribute :attr:`BottleneckProcessor.resample` (``'scipy'`` by default).  With
+``'kaldi'`` audio that is not at 8 kHz is uploaded at its own rate and resampled on the device by Kaldi's
+ResampleWaveform (``kernels_resample.hip``; cutoff 0.99 x half the lower rate, 6 zero crossings), a whole batch
+per rate in one launch, straight into the batch's 8 kHz block; the samples are converted to int16 *before*
+the resampling (after it on the default path) and the resampled length is Kaldi's (22 713 samples at 16 kHz
+give 11 357, the Fourier method 11 356).  With ``'scipy'`` nothing differs from before.
+
 Weights: the three published networks *BabelMulti*, *FisherMono* and *FisherTri* are ``.npz`` files of 17
 arrays that are not shipped with this package.  They are looked up under their published names in the
 directory named by the environment variable ``SHENNONG_AMD_BOTTLENECK_DIR`` and then in
@@ -238,16 +245,29 @@ class BottleneckBatch:
     intermediate buffers)"""
 
     def __init__(self, waves, device=None):
-        self.device = _backend.get_device() if device is None else int(device)
+        device = _backend.get_device() if device is None else int(device)
         waves = [np.ascontiguousarray(w, dtype=np.int16).reshape(-1) for w in waves]
-        self.n = len(waves)
-        self.soff = np.zeros(self.n + 1, dtype=np.int64)
-        np.cumsum([w.shape[0] for w in waves], out=self.soff[1:])
-        self.frames = np.array([num_frames(w.shape[0]) for w in waves], dtype=np.int64)
+        soff = np.zeros(len(waves) + 1, dtype=np.int64)
+        np.cumsum([w.shape[0] for w in waves], out=soff[1:])
+        self._layout(_backend.upload_rows(waves, np.int16, device), soff, device)
+
+    @classmethod
+    def from_device(cls, block, soff, device=None):
+        """The batch over 8 kHz int16 audio that is already on the device: utterance u is the samples
+        ``soff[u]:soff[u + 1]`` of the DeviceBuffer `block`"""
+        batch = cls.__new__(cls)
+        batch._layout(block, np.ascontiguousarray(soff, dtype=np.int64), block.device if device is None else device)
+        return batch
+
+    def _layout(self, block, soff, device):
+        self.device = int(device)
+        self.n = soff.shape[0] - 1
+        self.soff = soff
+        self.frames = np.array([num_frames(n) for n in np.diff(soff)], dtype=np.int64)
         self.foff = np.zeros(self.n + 1, dtype=np.int64)
         np.cumsum(self.frames, out=self.foff[1:])
         self.total_frames = int(self.foff[-1])
-        self.wave = _backend.upload_rows(waves, np.int16, self.device)
+        self.wave = block
         self.mask = self.voiced = self.logmel = self.x = self.bn = self.out = None
 
     def vad(self):
@@ -351,13 +371,15 @@ class BottleneckProcessor(FeaturesProcessor):
         If no weights file can be found
 
     Beyond the reference, the attribute :attr:`precision` (not a constructor parameter) selects how the hidden
-    layers are computed.
+    layers are computed, and the attribute :attr:`resample` (not one either) where and how audio that is not at
+    8 kHz is resampled.
     """
     def __init__(self, weights='BabelMulti', dither=0.1):
         super().__init__()
         self.weights = weights
         self.dither = dither
         self._precision = 'float32'
+        self._resample = 'scipy'
         self._network()
 
     @property
@@ -396,10 +418,25 @@ class BottleneckProcessor(FeaturesProcessor):
     def precision(self, value):
         self._precision = _check_precision(value)
 
+    @property
+    def resample(self):
+        """'scipy' (default) or 'kaldi': how audio that is not at 8 kHz gets there.  'scipy' is
+        :meth:`Audio.resample` on the host, one signal at a time, then the conversion to int16; 'kaldi'
+        converts to int16 first, uploads a batch at its own rate and runs Kaldi's ResampleWaveform on the
+        device (one more sample than the Fourier method for some lengths, and other values)"""
+        return self._resample
+
+    @resample.setter
+    def resample(self, value):
+        self._resample = _backend.check_resampler(value)
+
     def get_properties(self, **kwargs):
-        """The processor's properties; they record the precision when it is not the default"""
+        """The processor's properties; they record the precision and the resampler when they are not the
+        defaults"""
         if self._precision != 'float32':
             kwargs.setdefault('precision', self._precision)
+        if self._resample != 'scipy':
+            kwargs.setdefault('resample', self._resample)
         return super().get_properties(**kwargs)
 
     @property
@@ -494,6 +531,17 @@ class BottleneckProcessor(FeaturesProcessor):
             signal = signal.astype(np.int16)
         return np.ascontiguousarray(signal.data).reshape(-1)
 
+    def _samples_at_rate(self, signal):
+        """`signal` as int16 samples at its own rate, and that rate (:attr:`resample` 'kaldi': the conversion
+        to int16 comes before the resampling, which happens on the device)"""
+        if signal.nchannels != 1:
+            raise ValueError('signal must have one dimension, but it has {}'.format(signal.nchannels))
+        if signal.sample_rate != 8000 or signal.dtype != np.dtype(np.int16):
+            self.log.debug('resampling audio from %dHz@%db to %dHz@%db',
+                           signal.sample_rate, signal.dtype.itemsize * 8, 8000, 16)
+            signal = signal.astype(np.int16)
+        return np.ascontiguousarray(signal.data).reshape(-1), signal.sample_rate
+
     def process(self, signal):
         """Computes bottleneck features on an audio `signal` (mono; resampled to 8 kHz int16 if needed)
 
@@ -505,18 +553,26 @@ class BottleneckProcessor(FeaturesProcessor):
         device = _backend.get_device()
         dnet = self._device_network(device)
         context = dnet.net.context
-        waves = [self._samples(s) for s in signals]
+        if self._resample == 'kaldi':
+            waves, rates = zip(*[self._samples_at_rate(s) for s in signals]) if signals else ((), ())
+            lengths = _backend.native_lengths(waves, rates, 8000)
+        else:
+            waves = [self._samples(s) for s in signals]
+            lengths = [wave.shape[0] for wave in waves]
 
         def label(i):
             return '' if names is None else ' "{}"'.format(names[i])
 
-        for i, wave in enumerate(waves):
-            rows = num_frames(wave.shape[0]) + 2 * _EDGE - 2 * context - 20
-            if num_frames(wave.shape[0]) < 1 or rows < 1:
+        for i, length in enumerate(lengths):
+            rows = num_frames(length) + 2 * _EDGE - 2 * context - 20
+            if num_frames(length) < 1 or rows < 1:
                 raise ValueError(
                     'signal{} too short: {} samples at 8 kHz give {} frames, one row of features needs {}'.format(
-                        label(i), wave.shape[0], num_frames(wave.shape[0]), max(1, 2 * context + 21 - 2 * _EDGE)))
-        batch = BottleneckBatch(waves, device)
+                        label(i), length, num_frames(length), max(1, 2 * context + 21 - 2 * _EDGE)))
+        if self._resample == 'kaldi':
+            batch = BottleneckBatch.from_device(*_backend.upload_resampled(waves, rates, 8000, lengths, device))
+        else:
+            batch = BottleneckBatch(waves, device)
         voiced = batch.vad()
         for i, count in enumerate(voiced):
             if not count:

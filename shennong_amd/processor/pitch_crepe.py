@@ -13,6 +13,13 @@ bfloat16 matrix-core path for convolution blocks 2 to 6, nine tenths of the arit
 activations and kernels are rounded to bfloat16 (to nearest, ties to even) and the products accumulated in
 float32; the ingest, block 1, the classifier, the decoders and the host tail are the float32 path unchanged.
 
+Also beyond the reference: the attribute :attr:`CrepePitchProcessor.resample` (``'scipy'`` by default).  With
+``'kaldi'`` audio that is not at 16 kHz is uploaded at its own rate and resampled on the device by Kaldi's
+ResampleWaveform (``kernels_resample.hip``; cutoff 0.99 x half the lower rate, 6 zero crossings), a whole batch
+per rate in one launch, straight into the batch's 16 kHz block; the samples are converted to int16 *before*
+the resampling (after it on the default path) and the resampled length is Kaldi's.  The resampling of the
+output rows to the row count (``scipy.signal.resample``, on the host) is another operation and stays as it is.
+
 Weights: the five pretrained models are not shipped with this package.  ``model-<capacity>.npz`` is looked up
 in the directory named by the environment variable ``SHENNONG_AMD_CREPE_DIR`` and then in
 ``shennong_amd/share/crepe/``; ``tools/convert_crepe_h5.py`` writes that file from the published Keras
@@ -239,16 +246,30 @@ class CrepeBatch:
     :meth:`forward` then :meth:`decode` (the tests and ``tools/time_crepe.py`` read the intermediate buffers)"""
 
     def __init__(self, waves, hop, center=True, device=None):
-        self.device = _backend.get_device() if device is None else int(device)
+        device = _backend.get_device() if device is None else int(device)
         waves = [np.ascontiguousarray(w, dtype=np.int16).reshape(-1) for w in waves]
-        self.n, self.hop, self.center = len(waves), int(hop), bool(center)
-        self.soff = np.zeros(self.n + 1, dtype=np.int64)
-        np.cumsum([w.shape[0] for w in waves], out=self.soff[1:])
-        self.frames = np.array([num_frames(w.shape[0], self.hop, self.center) for w in waves], dtype=np.int64)
+        soff = np.zeros(len(waves) + 1, dtype=np.int64)
+        np.cumsum([w.shape[0] for w in waves], out=soff[1:])
+        self._layout(_backend.upload_rows(waves, np.int16, device), soff, hop, center, device)
+
+    @classmethod
+    def from_device(cls, block, soff, hop, center=True, device=None):
+        """The batch over 16 kHz int16 audio that is already on the device: utterance u is the samples
+        ``soff[u]:soff[u + 1]`` of the DeviceBuffer `block`"""
+        batch = cls.__new__(cls)
+        batch._layout(block, np.ascontiguousarray(soff, dtype=np.int64), hop, center,
+                      block.device if device is None else device)
+        return batch
+
+    def _layout(self, block, soff, hop, center, device):
+        self.device = int(device)
+        self.n, self.hop, self.center = soff.shape[0] - 1, int(hop), bool(center)
+        self.soff = soff
+        self.frames = np.array([num_frames(n, self.hop, self.center) for n in np.diff(soff)], dtype=np.int64)
         self.foff = np.zeros(self.n + 1, dtype=np.int64)
         np.cumsum(self.frames, out=self.foff[1:])
         self.total_frames = int(self.foff[-1])
-        self.wave = _backend.upload_rows(waves, np.int16, self.device)
+        self.wave = block
         self.activation = self.out = self.bins = None
 
     def forward(self, model, precision='float32'):
@@ -353,12 +374,14 @@ class CrepePitchProcessor(FeaturesProcessor):
     and two columns corresponding to (POV, pitch). POV is the Probability of Voicing.
 
     Beyond the reference, the attribute :attr:`precision` (not a constructor parameter) selects how convolution
-    blocks 2 to 6 are computed.
+    blocks 2 to 6 are computed, and the attribute :attr:`resample` (not one either) where and how audio that is
+    not at 16 kHz is resampled.
     """
     def __init__(self, model_capacity='full', viterbi=True, center=True,
                  frame_shift=0.01, frame_length=0.025):
         super().__init__()
         self._precision = 'float32'
+        self._resample = 'scipy'
         self.model_capacity = model_capacity
         self.viterbi = viterbi
         self.center = center
@@ -429,10 +452,25 @@ class CrepePitchProcessor(FeaturesProcessor):
     def precision(self, value):
         self._precision = _check_precision(value)
 
+    @property
+    def resample(self):
+        """'scipy' (default) or 'kaldi': how audio that is not at 16 kHz gets there.  'scipy' is
+        :meth:`Audio.resample` on the host, one signal at a time, then the conversion to int16; 'kaldi'
+        converts to int16 first, uploads a batch at its own rate and runs Kaldi's ResampleWaveform on the
+        device (one more sample than the Fourier method for some lengths, and other values)"""
+        return self._resample
+
+    @resample.setter
+    def resample(self, value):
+        self._resample = _backend.check_resampler(value)
+
     def get_properties(self, **kwargs):
-        """The processor's properties; they record the precision when it is not the default"""
+        """The processor's properties; they record the precision and the resampler when they are not the
+        defaults"""
         if self._precision != 'float32':
             kwargs.setdefault('precision', self._precision)
+        if self._resample != 'scipy':
+            kwargs.setdefault('resample', self._resample)
         return super().get_properties(**kwargs)
 
     @property
@@ -459,6 +497,15 @@ class CrepePitchProcessor(FeaturesProcessor):
             audio = audio.resample(self.sample_rate)
         return np.ascontiguousarray(audio.astype(np.int16).data).reshape(-1)
 
+    def _samples_at_rate(self, audio):
+        """`audio` as int16 samples at its own rate, and that rate (:attr:`resample` 'kaldi': the conversion
+        to int16 comes before the resampling, which happens on the device)"""
+        if audio.nchannels != 1:
+            raise ValueError(f'audio must have one channel but has {audio.nchannels}')
+        if audio.sample_rate != self.sample_rate:
+            self.log.debug('resampling audio to 16 kHz')
+        return np.ascontiguousarray(audio.astype(np.int16).data).reshape(-1), audio.sample_rate
+
     def _output_rows(self, nsamples):
         """Rows of the output for a signal of `nsamples` at 16 kHz (reference pitch_crepe.py:473-476)"""
         hop = np.round(self.sample_rate * self.frame_shift).astype(int)
@@ -473,23 +520,32 @@ class CrepePitchProcessor(FeaturesProcessor):
 
     def _process_batch(self, signals, names=None):
         import scipy.signal
-        waves = [self._samples(s) for s in signals]
+        if self._resample == 'kaldi':
+            waves, rates = zip(*[self._samples_at_rate(s) for s in signals]) if signals else ((), ())
+            lengths = _backend.native_lengths(waves, rates, self.sample_rate)
+        else:
+            waves = [self._samples(s) for s in signals]
+            lengths = [wave.shape[0] for wave in waves]
         hop = int(self.sample_rate * self.frame_shift)
         if hop < 1:
             raise ValueError(f'frame_shift must be at least one sample at 16 kHz, it is {self.frame_shift}')
-        for i, wave in enumerate(waves):
-            if num_frames(wave.shape[0], hop, self.center) < 1 or self._output_rows(wave.shape[0]) < 1:
+        for i, length in enumerate(lengths):
+            if num_frames(length, hop, self.center) < 1 or self._output_rows(length) < 1:
                 label = '' if names is None else ' "{}"'.format(names[i])
-                raise ValueError(f'audio{label} too short: {wave.shape[0]} samples at 16 kHz')
+                raise ValueError(f'audio{label} too short: {length} samples at 16 kHz')
         device = _backend.get_device()
         model = device_model(self.model_capacity, device)
-        batch = CrepeBatch(waves, hop, self.center, device)
+        if self._resample == 'kaldi':
+            batch = CrepeBatch.from_device(
+                *_backend.upload_resampled(waves, rates, self.sample_rate, lengths, device), hop, self.center)
+        else:
+            batch = CrepeBatch(waves, hop, self.center, device)
         batch.forward(model, self._precision)
         raw = batch.decode(self.viterbi)
         properties = self.get_properties()
         feats = []
-        for wave, a, b in zip(waves, batch.foff[:-1], batch.foff[1:]):
-            data = scipy.signal.resample(raw[a:b], self._output_rows(wave.shape[0]))
+        for length, a, b in zip(lengths, batch.foff[:-1], batch.foff[1:]):
+            data = scipy.signal.resample(raw[a:b], self._output_rows(length))
             # hack needed because resample confidence
             data[data[:, 0] < 1e-2, 0] = 0
             data[data[:, 0] > 1, 0] = 1
