@@ -556,6 +556,41 @@ int snf_crepe_forward_bf16(int device_id, const int16_t* d_wave, const int64_t* 
  * d_bins[2 x total_frames] int32 (first argmax, chosen bin). */
 int snf_crepe_decode(int device_id, const float* d_activation, const int64_t* h_frame_offsets, int64_t n_utts,
                      int32_t viterbi, const double* d_tables, double* d_out, int32_t* d_bins, void* stream);
+/* The tail between the decoder and the Kaldi post-processing (reference pitch_crepe.py:473-489, :572-606), float64
+ * on the device; the host layer runs snf_crepe_rows before snf_crepe_voicing_convert.
+ *
+ * Row resampling by the Fourier method plus the reference's clamp: utterance u, the N rows
+ * [h_in_offsets[u], h_in_offsets[u + 1]) of d_in[total_in x 2] (confidence, Hertz: the layout of snf_crepe_decode's
+ * d_out), becomes the M rows [h_out_offsets[u], h_out_offsets[u + 1]) of d_out[total_out x 2].  N >= 1 and M >= 1
+ * (anything else is SNF_E_INVALID), both at most 2^20.  Each column is scipy.signal.resample(x, M) of real input:
+ * the input bits when M == N, otherwise with L = min(N, M), K = (L - 1) / 2 and theta(m, n) = 2 pi (m / M - n / N)
+ *     y[m] = (1 / N) sum_n x[n] D(m, n),   D = 1 + 2 sum_{k = 1..K} cos(k theta) + c cos((L / 2) theta),
+ * c = 0 for odd L, 2 for even L when M < N, 1 for even L when M > N.  D is evaluated in its closed form
+ * sin((2K + 1) theta / 2) / sin(theta / 2) + c cos((L / 2) theta) (2K + 1 + c where theta is a multiple of 2 pi),
+ * every angle a fraction of pi reduced in integers modulo 2 M N before sinpi / cospi see it; the N terms of a row
+ * are added in ascending n, so an utterance gives the same bits alone and in any batch.  Then column 0 is
+ * clamped: values below 1e-2 become 0, values above 1 become 1.  Buffers 8-byte aligned. */
+int snf_crepe_rows(int device_id, const double* d_in, const int64_t* h_in_offsets, const int64_t* h_out_offsets,
+                   int64_t n_utts, double* d_out, void* stream);
+/* CrepePitchPostProcessor's conversion of d_rows[total x 2] float64 (POV, Hertz; the output of snf_crepe_rows) into
+ * d_out[total x 2] float32 (NCCF, pitch), the input of the Kaldi post-processing; utterance u is the rows
+ * [h_offsets[u], h_offsets[u + 1]).  Per utterance:
+ *  1. the most likely voiced / unvoiced state per frame under a two-state model, float64 log domain, no fused
+ *     multiply-add, first index on ties: log emission of state s = -0.5 * (h_model[0] + (pov - mean_s)^2 /
+ *     variance), lattice[0] = log_start + emission, lattice[t][j] = max_i(lattice[t - 1][i] + logA[i][j]) +
+ *     emission[t][j], states read back from the lattice.  h_model[11] (HOST float64): log(2 pi variance), mean_0,
+ *     mean_1, variance, log_start, logA[0][0], logA[0][1], logA[1][0], logA[1][1], then f(0) and f(1) of step 3;
+ *  2. the pitch of the unvoiced frames by linear interpolation between the nearest voiced neighbours
+ *     (slope * (t - t_before) + pitch_before), the value of the first / last voiced frame outside them;
+ *  3. NCCF from POV: 0 and 1 map to themselves, everything else by 64 halvings of [0, 1] over
+ *     f(x) = 1 / (1 + exp(-(-5.2 + 5.4 exp(7.5 (x - 1)) + 4.8 x - 2 exp(-10 x) + 4.2 exp(20 (x - 1)))));
+ *  4. d_status[u] int32: 0 fine, 1 no voiced frame, 2 a pitch value that is not > 0 after the interpolation,
+ *     3 a POV other than 0 and 1 outside (f(0), f(1)); the lowest that applies.  A non-zero status leaves the
+ *     utterance's output rows finite or zero (1 and 2: zero) and touches no other utterance.
+ * An utterance with one row is valid; one without rows gets status 0 and writes nothing.  At most 2^30 rows per
+ * utterance.  d_rows 8-byte, d_out and d_status 4-byte aligned. */
+int snf_crepe_voicing_convert(int device_id, const double* d_rows, const int64_t* h_offsets, int64_t n_utts,
+                              const double* h_model, float* d_out, int32_t* d_status, void* stream);
 
 /* ---- framed one-hot labels (reference processor/onehot.py, FramedOneHotProcessor) -------------------
  * Per-frame labels of a batch of time alignments, one call for the whole batch.  Alignment a holds segments

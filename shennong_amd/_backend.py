@@ -47,7 +47,8 @@ EXPORTS = [
     'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward', 'snf_crepe_conv',
     'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot', 'snf_packed_weights_bf16_size',
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
-    'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample']
+    'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
+    'snf_crepe_voicing_convert']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -187,6 +188,8 @@ def lib():
                                           i32, vp]
         L.snf_crepe_forward_bf16.argtypes = [i32, vp, pi64, i64, i32, i32, pi32, C.POINTER(vp), vp, vp]
         L.snf_crepe_decode.argtypes = [i32, vp, pi64, i64, i32, vp, vp, vp, vp]
+        L.snf_crepe_rows.argtypes = [i32, vp, pi64, pi64, i64, vp, vp]
+        L.snf_crepe_voicing_convert.argtypes = [i32, vp, pi64, i64, pf64, vp, vp, vp]
         L.snf_framed_onehot.argtypes = [i32, C.c_double, i32, i32, i32, f32, i64, pi64, pf64, pf64, pi32, pi64, pi64,
                                         pi32, pi64, vp, vp, pf, vp]
         L.snf_resample_num_out.argtypes = [i32, i32, i64]

@@ -204,4 +204,75 @@ int snf_crepe_decode(int device_id, const float* d_activation, const int64_t* h_
   return lay.finish(rc, "crepe decoder kernels failed");
 }
 
+int snf_crepe_rows(int device_id, const double* d_in, const int64_t* h_in_offsets, const int64_t* h_out_offsets,
+                   int64_t n_utts, double* d_out, void* stream) {
+  int rc = crepe_check_offsets(h_in_offsets, n_utts, "input row");
+  if (!rc) rc = crepe_check_offsets(h_out_offsets, n_utts, "output row");
+  if (rc) return rc;
+  constexpr int64_t kMaxRows = int64_t(1) << 20;   // (M N (2K + 1) must fit an int64)
+  int64_t n_tiles = 0;
+  for (int64_t u = 0; u < n_utts; ++u) {
+    const int64_t N = h_in_offsets[u + 1] - h_in_offsets[u], M = h_out_offsets[u + 1] - h_out_offsets[u];
+    if (N < 1 || M < 1)
+      return set_error(SNF_E_INVALID, "crepe rows: utterance " + std::to_string(u) + " has no input or no output rows");
+    if (N > kMaxRows || M > kMaxRows)
+      return set_error(SNF_E_INVALID, "crepe rows: utterance " + std::to_string(u) + " has more than 2^20 rows");
+    n_tiles += (M + kCrepeRowsTile - 1) / kCrepeRowsTile;
+  }
+  if (n_tiles > (int64_t(1) << 30)) return set_error(SNF_E_INVALID, "crepe: batch too large");
+  if (n_utts == 0) return SNF_OK;
+  if (!d_in || !d_out) return set_error(SNF_E_INVALID, "crepe: null buffer");
+  if ((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out)) & 7)
+    return set_error(SNF_E_INVALID, "crepe rows: a buffer is not 8-byte aligned");
+  std::vector<int64_t> tile_off(n_utts + 1, 0);
+  std::vector<int32_t> tile_utt(n_tiles);
+  for (int64_t u = 0; u < n_utts; ++u) {
+    const int64_t M = h_out_offsets[u + 1] - h_out_offsets[u];
+    tile_off[u + 1] = tile_off[u] + (M + kCrepeRowsTile - 1) / kCrepeRowsTile;
+    std::fill(tile_utt.begin() + tile_off[u], tile_utt.begin() + tile_off[u + 1], static_cast<int32_t>(u));
+  }
+  Planless lay;
+  auto d_ioff = lay.take<int64_t>(n_utts + 1);
+  auto d_ooff = lay.take<int64_t>(n_utts + 1);
+  auto d_toff = lay.take<int64_t>(n_utts + 1);
+  auto d_tutt = lay.take<int32_t>(n_tiles);
+  if ((rc = lay.begin(device_id, stream))) return rc;
+  const size_t table = sizeof(int64_t) * (n_utts + 1);
+  SNF_HIP_CHECK(hipMemcpyAsync(d_ioff, h_in_offsets, table, hipMemcpyHostToDevice, lay.s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_ooff, h_out_offsets, table, hipMemcpyHostToDevice, lay.s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_toff, tile_off.data(), table, hipMemcpyHostToDevice, lay.s));
+  SNF_HIP_CHECK(hipMemcpyAsync(d_tutt, tile_utt.data(), sizeof(int32_t) * n_tiles, hipMemcpyHostToDevice, lay.s));
+  rc = launch_crepe_rows(d_in, d_ioff, d_ooff, d_tutt, d_toff, n_tiles, d_out, lay.s);
+  // (the wait below also covers the copies out of tile_off / tile_utt, which are pageable)
+  return lay.finish(rc, "crepe row resampling kernel failed");
+}
+
+int snf_crepe_voicing_convert(int device_id, const double* d_rows, const int64_t* h_offsets, int64_t n_utts,
+                              const double* h_model, float* d_out, int32_t* d_status, void* stream) {
+  int rc = crepe_check_offsets(h_offsets, n_utts, "row");
+  if (rc) return rc;
+  if (!h_model) return set_error(SNF_E_INVALID, "crepe voicing: null model");
+  for (int i = 0; i < kCrepeVoicingModel; ++i)
+    if (!(h_model[i] == h_model[i])) return set_error(SNF_E_INVALID, "crepe voicing: the model holds a NaN");
+  if (!(h_model[3] > 0)) return set_error(SNF_E_INVALID, "crepe voicing: the variance must be positive");
+  for (int64_t u = 0; u < n_utts; ++u)
+    if (h_offsets[u + 1] - h_offsets[u] > (int64_t(1) << 30))
+      return set_error(SNF_E_INVALID, "crepe voicing: utterance " + std::to_string(u) + " has more than 2^30 rows");
+  if (n_utts > (int64_t(1) << 30)) return set_error(SNF_E_INVALID, "crepe: batch too large");
+  if (n_utts == 0) return SNF_OK;
+  const int64_t total = h_offsets[n_utts];
+  if (!d_status || (total > 0 && (!d_rows || !d_out))) return set_error(SNF_E_INVALID, "crepe: null buffer");
+  if ((reinterpret_cast<uintptr_t>(d_rows) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 3) ||
+      (reinterpret_cast<uintptr_t>(d_status) & 3))
+    return set_error(SNF_E_INVALID, "crepe voicing: a buffer is not aligned to its element type");
+  Planless lay;
+  auto d_off = lay.take<int64_t>(n_utts + 1);
+  auto lattice = lay.take<double>(2 * total);
+  auto next_voiced = lay.take<int32_t>(total);
+  if ((rc = lay.begin(device_id, stream))) return rc;
+  SNF_HIP_CHECK(hipMemcpyAsync(d_off, h_offsets, sizeof(int64_t) * (n_utts + 1), hipMemcpyHostToDevice, lay.s));
+  rc = launch_crepe_voicing(d_rows, d_off, n_utts, h_model, lattice, next_voiced, d_out, d_status, lay.s);
+  return lay.finish(rc, "crepe voicing kernel failed");
+}
+
 }  // extern "C"

@@ -454,6 +454,18 @@ int launch_crepe_decode(const float* act, const int64_t* foff, int64_t n_utts, i
                         const double* tab, float* conf, uint16_t* psi, int32_t* bins, double* out,
                         hipStream_t stream);
 
+// The tail of the CREPE path (kernels_crepe_tail.hip): see that file's header for the design
+constexpr int kCrepeRowsTile = 64;          // output rows of one workgroup of the row resampler (a row per lane)
+constexpr int kCrepeRowsStage = 1024;       // input rows it holds in LDS at a time
+constexpr int kCrepeVoicingChunk = 1024;    // frames of the voicing lattice staged in LDS at a time
+constexpr int kCrepeVoicingModel = 11;      // float64 entries of the voicing model (include/shennong_amd.h)
+// tile k (one workgroup) belongs to utterance tile_utt[k], whose first tile is tile_off[utterance]
+int launch_crepe_rows(const double* in, const int64_t* in_off, const int64_t* out_off, const int32_t* tile_utt,
+                      const int64_t* tile_off, int64_t n_tiles, double* out, hipStream_t stream);
+// h_model: HOST; lattice[total x 2] and next_voiced[total] scratch; out[total x 2] (NCCF, pitch), status[n_utts]
+int launch_crepe_voicing(const double* rows, const int64_t* off, int64_t n_utts, const double* h_model,
+                         double* lattice, int32_t* next_voiced, float* out, int32_t* status, hipStream_t stream);
+
 // Framed one-hot labels (kernels_onehot.hip): see that file's header for the design.  Device pointers; the
 // caller (capi_onehot.hip) has checked on the host everything the kernels index with.
 constexpr int kOneHotMaxFrameLength = 8192;   // samples per frame: the window sits in LDS

@@ -18,9 +18,18 @@ be given instead (``warps=...``), not both.  ``get_default_config(with_vtln=...)
 here; build it as ``config['vtln'] = VtlnProcessor().get_params()``.  The sharded entry points
 (:mod:`shennong_amd.distributed`) take precomputed warps only.
 
-Not provided by this pipeline: CREPE pitch and bottleneck features (the processors exist -
-:class:`shennong_amd.processor.pitch_crepe.CrepePitchProcessor`,
-:class:`shennong_amd.processor.bottleneck.BottleneckProcessor` - but are not pipeline entries yet).
+A 'pitch' entry with ``processor: crepe`` (:func:`get_crepe_pitch_config` writes it;
+``get_default_config(with_pitch='crepe')`` does not) runs the CREPE tracker beside the features like the Kaldi
+one, everything between the audio and the pitch columns on the device: network, decoder, the resampling of the
+rows to the row count, the voicing model, the interpolation, the POV -> NCCF conversion and the Kaldi
+post-processing (:class:`shennong_amd.processor.pitch_crepe.CrepeBatch`).  An extension: audio that is not at
+16 kHz is brought there by the device resampler (Kaldi's ResampleWaveform, ``kernels_resample.hip``), not by
+the host's Fourier method - in the streamed second pass and for pinned corpora the audio exists in HBM only -
+and the pitch properties record it as ``resample: 'kaldi'``, exactly as a
+:class:`~shennong_amd.processor.pitch_crepe.CrepePitchProcessor` with ``resample = 'kaldi'`` does.
+
+Not provided by this pipeline: bottleneck features (the processor exists -
+:class:`shennong_amd.processor.bottleneck.BottleneckProcessor` - but is not a pipeline entry yet).
 """
 
 import os
@@ -44,6 +53,8 @@ _PROCESSORS = {
     'mfcc': ('processor', 'MfccProcessor'),
     'kaldi_pitch': ('processor', 'KaldiPitchProcessor'),
     'kaldi_pitch_post': ('processor', 'KaldiPitchPostProcessor'),
+    'crepe_pitch': ('processor', 'CrepePitchProcessor'),
+    'crepe_pitch_post': ('processor', 'CrepePitchPostProcessor'),
     'plp': ('processor', 'PlpProcessor'),
     'spectrogram': ('processor', 'SpectrogramProcessor'),
     'cmvn': ('postprocessor', 'CmvnPostProcessor'),
@@ -78,6 +89,9 @@ def get_default_config(features, to_yaml=False, yaml_commented=True,
     Same dictionary layout as the reference (one entry per processor, parameters with their default
     values, `sample_rate` and `htk_compat` filtered out of the features entry, frame parameters
     filtered out of the pitch entry).
+
+    ``with_pitch='crepe'`` is refused here.  The pipeline itself does take a CREPE pitch entry: add one to the
+    returned configuration as ``config['pitch'] = get_crepe_pitch_config()``.
 
     `with_vtln` is refused here.  The pipeline itself does train VTLN warps from a 'vtln' entry: add one to
     the returned configuration as ``config['vtln'] = VtlnProcessor().get_params()`` (or with
@@ -129,6 +143,27 @@ def get_default_config(features, to_yaml=False, yaml_commented=True,
     if to_yaml:
         return _get_config_to_yaml(config, comments=yaml_commented)
     return config
+
+
+def get_crepe_pitch_config():
+    """The 'pitch' entry of a configuration for CREPE pitch, as the reference's
+    ``get_default_config(..., with_pitch='crepe')`` writes it: ``processor: crepe``, the parameters of
+    :class:`~shennong_amd.processor.pitch_crepe.CrepePitchProcessor` without the frame parameters (the
+    features' are used) and, under 'postprocessing', those of
+    :class:`~shennong_amd.processor.pitch_crepe.CrepePitchPostProcessor`.  Loads no weights."""
+    entry = {'processor': 'crepe'}
+    for key, value in _processor_params('crepe_pitch').items():
+        if key not in ('frame_length', 'frame_shift', 'sample_rate'):
+            entry[key] = value
+    entry['postprocessing'] = _processor_params('crepe_pitch_post')
+    return entry
+
+
+def _pitch_processors(config):
+    """The names (in _PROCESSORS) of the pitch processor and post-processor of `config`: CREPE's for
+    ``processor: crepe``, Kaldi's for anything else (reference pipeline_manager.py:291-308)"""
+    kind = 'crepe' if config['pitch'].get('processor', 'kaldi') == 'crepe' else 'kaldi'
+    return f'{kind}_pitch', f'{kind}_pitch_post'
 
 
 def _get_config_to_yaml(config, comments=True):
@@ -247,14 +282,22 @@ def _init_config(config, log=get_logger('pipeline', 'warning')):
             config['cmvn']['with_vad'] = True
 
     if 'pitch' in config:
-        if config['pitch'].get('processor', 'kaldi') != 'kaldi':
-            raise ValueError('only the kaldi pitch processor is available in this backend')
         if 'postprocessing' not in config['pitch']:
             config['pitch']['postprocessing'] = {}
+        if config['pitch'].get('processor', 'kaldi') == 'crepe':
+            # (the Kaldi entry is validated where its processors are made, like in the reference; the CREPE one
+            # here: its processors are made on a side thread, after the first launches of the batch)
+            names = _pitch_processors(config)
+            params = {k: v for k, v in config['pitch'].items() if k not in ('processor', 'postprocessing')}
+            try:
+                _processor_class(names[0])(**params)
+                _processor_class(names[1])(**config['pitch']['postprocessing'])
+            except (TypeError, ValueError) as err:
+                raise ValueError(f'error in configuration: crepe pitch: {err}') from None
 
     msg = []
     if 'pitch' in config:
-        msg.append('kaldi pitch')
+        msg.append('{} pitch'.format(config['pitch'].get('processor', 'kaldi')))
     if 'delta' in config:
         msg.append('delta')
     if 'cmvn' in config:
@@ -342,7 +385,7 @@ def extract_features(configuration, utterances, warps=None, njobs=1,
     log.info('detected format for utterances index is: %s',
              utterances.format(type=str))
     warps, config = _train_vtln(config, utterances, warps, njobs, log)
-    if _too_large_for_one_batch(utterances):
+    if _sized(_too_large_for_one_batch, utterances, config):
         # the corpus in one launch per stage would not fit the HBM that is free (the pitch tracker alone keeps
         # 2.3 GB of scratch per hour of audio): the same features - bit for bit, see extract_features_streamed -
         # from bounded batches, collected here (the reference, on the CPU, takes a corpus of any size)
@@ -355,12 +398,13 @@ def extract_features(configuration, utterances, warps=None, njobs=1,
     return _extract_features(config, _view_of(utterances), warps, log)
 
 
-def _too_large_for_one_batch(utterances):
+def _too_large_for_one_batch(utterances, extra_bytes_per_hour=0):
     """True when one batch over all of `utterances` would need more than half of the HBM that is free
-    (_BATCH_BYTES_PER_HOUR per hour of audio while a batch is in flight)"""
+    (_BATCH_BYTES_PER_HOUR per hour of audio while a batch is in flight, plus `extra_bytes_per_hour`: a CREPE
+    pitch entry, :func:`_crepe_bytes_per_hour`)"""
     if _backend.device_count() < 1:   # (host-logic tests with the device pipeline replaced by a stand-in)
         return False
-    need = utterances.duration() / 3600.0 * _BATCH_BYTES_PER_HOUR
+    need = utterances.duration() / 3600.0 * (_BATCH_BYTES_PER_HOUR + extra_bytes_per_hour)
     if need < (8 << 30):              # (no query for what certainly fits)
         return False
     free, _ = _backend.mem_info()
@@ -490,15 +534,46 @@ _BATCH_BYTES_PER_HOUR = 4 << 30   # HBM one hour of audio needs while its batch 
                                   # scratch (19 GB per 10 000 x 3 s), audio, features, CMVN / delta copies
 
 
-def default_batch_duration(depth=1):
+# What the CREPE tracker's job (_CrepeTracker) holds per NETWORK frame while it runs, on top of the above: the
+# activation [360] float32 = 1440 bytes; its (confidence, Hertz) float64 rows 16 and bins 2 x int32 = 8; per OUTPUT
+# row (about one per network frame) the resampled float64 rows 16, the (NCCF, pitch) float32 rows 8 and the
+# post-processed pitch 4 x 4; and the calling thread's scratch, which every entry point reuses and which therefore
+# counts once, at its largest: the decoder's Viterbi back pointers [360] uint16 = 720 and confidence 4 (the voicing
+# kernel's lattice 16 and neighbour table 4 per row fit in the same block; the network's own scratch is bounded,
+# 512 MiB).  2228 bytes in all.  A group that is not at 16 kHz also holds its 16 kHz copy from the device resampler,
+# 2 bytes a sample: the rate of the audio is not known where the batches are sized, so every hour counts it.
+_CREPE_BYTES_PER_FRAME = 1440 + 16 + 8 + 16 + 8 + 16 + (720 + 4)
+_CREPE_NATIVE_COPY_PER_HOUR = 2 * 16000 * 3600
+
+
+def _crepe_bytes_per_hour(config):
+    """HBM an hour of audio needs on top of _BATCH_BYTES_PER_HOUR when the pitch entry of `config` is CREPE: 0
+    otherwise (:func:`_sized` passes it on only when there is any: callers that replace the two estimates by
+    one-argument functions keep working for every other configuration)"""
+    if 'pitch' not in config or config['pitch'].get('processor', 'kaldi') != 'crepe':
+        return 0
+    features = [k for k in config.keys() if k in valid_features()][0]
+    shift = float(config[features].get('frame_shift', 0.01))
+    return int(round(3600.0 / max(shift, 1.0 / 16000))) * _CREPE_BYTES_PER_FRAME + _CREPE_NATIVE_COPY_PER_HOUR
+
+
+def _sized(estimate, what, config):
+    """``estimate(what)`` of :func:`_too_large_for_one_batch` / :func:`default_batch_duration`, with the CREPE
+    entry's bytes per hour when `config` has one"""
+    extra = _crepe_bytes_per_hour(config)
+    return estimate(what, extra) if extra else estimate(what)
+
+
+def default_batch_duration(depth=1, extra_bytes_per_hour=0):
     """Seconds of audio per streamed batch when the caller names none: four hours (measured best on a
     288 GB MI355X, see extract_features_streamed) unless `depth` such batches in flight would need more than
-    half of the HBM that is free right now (_BATCH_BYTES_PER_HOUR each) - smaller devices get smaller batches
-    instead of an out-of-memory error half way through a corpus; never below ten minutes."""
+    half of the HBM that is free right now (_BATCH_BYTES_PER_HOUR each, plus `extra_bytes_per_hour`: a CREPE
+    pitch entry) - smaller devices get smaller batches instead of an out-of-memory error half way through a
+    corpus; never below ten minutes."""
     if _backend.device_count() < 1:   # (host-logic tests with the device pipeline replaced by a stand-in)
         return 14400.0
     free, _ = _backend.mem_info()
-    hours = (free // 2) / float(_BATCH_BYTES_PER_HOUR * max(int(depth), 1))
+    hours = (free // 2) / float((_BATCH_BYTES_PER_HOUR + extra_bytes_per_hour) * max(int(depth), 1))
     return float(min(14400.0, max(600.0, 3600.0 * hours)))
 
 
@@ -556,7 +631,7 @@ def extract_features_streamed(configuration, utterances, sink, warps=None,
             'but no speaker information provided')
     utts = list(utterances)
     if max_batch_duration is None:
-        max_batch_duration = default_batch_duration(depth)
+        max_batch_duration = _sized(default_batch_duration, depth, config)
     has_speakers, pinned = utterances.has_speakers(), getattr(utterances, '_pinned', None)
     all_names, all_speakers = [u.name for u in utts], [u.speaker for u in utts]
 
@@ -922,10 +997,99 @@ class _Tracker:
         self.job = _backend.side_pool().submit(track) if start else None   # (not started: the description only)
 
 
+class _WaveView:
+    """A block of resident audio known by its address alone, with what the resampler and CrepeBatch read of a
+    DeviceBuffer; it owns nothing"""
+    def __init__(self, ptr, nbytes, device):
+        self.ptr, self.nbytes, self.device = ptr, nbytes, device
+
+
+class _CrepeTracker:
+    """The CREPE counterpart of :class:`_Tracker`, same interface (`names`: of the block's utterances, for the
+    messages).  The job, on the side pool: [the device resampler to 16 kHz for a block at another rate ->] the
+    network -> the decoder, its rows left on the device -> the rows resampled to the row count -> voicing,
+    interpolation and NCCF -> the Kaldi post-processing; `job.result()` is the [frames, pdim] device block.  What
+    can be refused from the lengths alone (a frame shift below one sample, an utterance that is too short) is
+    refused here, before any launch."""
+    def __init__(self, config, rate, frame_shift, frame_length, d_wave, soff, stats=None, start=True, names=None):
+        from shennong_amd.processor import pitch_crepe
+        DB = _backend.DeviceBuffer
+        params = {k: v for k, v in config['pitch'].items() if k not in ('processor', 'postprocessing')}
+        params['frame_shift'] = frame_shift
+        params['frame_length'] = frame_length
+        self.rate, self.soff = rate, soff
+        self.pproc = pproc = _processor_class('crepe_pitch')(**params)
+        self.post = post = _processor_class('crepe_pitch_post')(**config['pitch']['postprocessing'])
+        native = pproc.sample_rate
+        if rate != native:
+            pproc.resample = 'kaldi'   # (what the job does; the properties record it)
+        hop = int(native * pproc.frame_shift)
+        if hop < 1:
+            raise ValueError(f'frame_shift must be at least one sample at 16 kHz, it is {pproc.frame_shift}')
+        lengths = np.diff(soff)
+        if rate != native:
+            uniq, inverse = np.unique(lengths, return_inverse=True)
+            lengths = np.asarray([_backend.resample_num_out(rate, native, x) for x in uniq.tolist()],
+                                 dtype=np.int64)[inverse]
+        for i, length in enumerate(lengths.tolist()):
+            if pitch_crepe.num_frames(length, hop, pproc.center) < 1 or pproc._output_rows(length) < 1:
+                label = '' if names is None else ' "{}"'.format(names[i])
+                raise ValueError(f'audio{label} too short: {length} samples at 16 kHz')
+        counts = np.asarray([pproc._output_rows(x) for x in lengths.tolist()], dtype=np.int64)
+        self.pfoff = pfoff = _offsets(counts)
+        qplan = _backend.get_plan(post._build_options())
+        self.pdim = pdim = qplan.post_ndims(2)
+        device = _backend.get_device()
+
+        def track():
+            d_native = batch = d_pitch = None
+            try:
+                model = pitch_crepe.device_model(pproc.model_capacity, device)
+                t0 = time.perf_counter()
+                wave, soff16 = _WaveView(d_wave, 2 * int(soff[-1]), device), soff
+                if rate != native:
+                    d_native, soff16 = _backend.resample_device(wave, soff, rate, native, 0)
+                    wave = d_native
+                batch = pitch_crepe.CrepeBatch.from_device(wave, soff16, hop, pproc.center, device)
+                batch.forward(model, pproc.precision)
+                batch.decode(pproc.viterbi, resident=True)
+                batch.rows(counts)
+                batch.convert()
+                d_pitch = DB(max(int(pfoff[-1]) * pdim * 4, 16))
+                qplan.run_post_device(batch.nccf_pitch.ptr, 2, pfoff, d_pitch.ptr, noise_call=_NOISE_CALL)
+                if stats is not None:
+                    # the plan-less CREPE entry points record no events: the time of the calls on this thread,
+                    # each of which returns when its stream is idle - the resampler, the network, the decoder, the
+                    # two tail kernels and the post-processing, with their launch overhead
+                    stats.add(gpu_ms=1e3 * (time.perf_counter() - t0))
+            except BaseException:
+                # (as in _Tracker: something may still be enqueued on these blocks, the plain free() waits)
+                if batch is not None:
+                    batch.release()
+                for block in (d_pitch, d_native):
+                    if block is not None:
+                        block.free()
+                raise
+            batch.release(synced=True)   # (every call returned: their streams are synchronised)
+            if d_native is not None:
+                d_native.free(synced=True)
+            return d_pitch
+
+        self.job = _backend.side_pool().submit(track) if start else None   # (not started: the description only)
+
+
+def _make_tracker(config, *args, names=None, **kwargs):
+    """The tracker of the configuration's pitch processor"""
+    if _pitch_processors(config)[0] == 'crepe_pitch':
+        return _CrepeTracker(config, *args, names=names, **kwargs)
+    return _Tracker(config, *args, **kwargs)
+
+
 class RunStats:
     """What a pipeline run cost, summed over its batches and threads (pass one as ``stats=`` to
     :func:`extract_features_streamed`): bytes over the host link in each direction, seconds this process
-    waited for uploads / downloads, milliseconds of kernels (HIP events of every plan call).  bench.py prints
+    waited for uploads / downloads, milliseconds of kernels (HIP events of every plan call; for a CREPE pitch entry, whose entry points record no
+    events, the host's clock around the calls of its job, see _CrepeTracker).  bench.py prints
     them beside the wall clock: the link floor and the GPU time of BASELINE config 5."""
     _FIELDS = ('bytes_up', 'bytes_down', 'upload_wait_s', 'download_wait_s', 'gpu_ms', 'batches', 'utterances')
 
@@ -1122,8 +1286,8 @@ class _PipelineRun:
                     # for uploads, the second for downloads - the GPU is idle in the first
                     self.resident.offer_track(
                         (self.batch_id, group.rate),
-                        _Tracker(self.config, group.rate, self.frame_shift, self.frame_length, block.ptr,
-                                 group.soff, self.stats).job)
+                        _make_tracker(self.config, group.rate, self.frame_shift, self.frame_length, block.ptr,
+                                      group.soff, self.stats, names=[self.names[i] for i in group.idx.tolist()]).job)
             else:
                 group.drop('wave')
         if self.with_cmvn:
@@ -1243,8 +1407,9 @@ class _PipelineRun:
     def stage_pitch_start(self, group):
         cache, rate = self.cache, group.rate
         made = self.resident.take_track((self.batch_id, rate)) if self.resident is not None else None
-        tracker = _Tracker(self.config, rate, self.frame_shift, self.frame_length, group.ptr('wave'), group.soff,
-                           self.stats, start=made is None)
+        tracker = _make_tracker(self.config, rate, self.frame_shift, self.frame_length, group.ptr('wave'),
+                                group.soff, self.stats, start=made is None,
+                                names=[self.names[i] for i in group.idx.tolist()])
         group.pfoff, group.pdim, group.pitch_job = tracker.pfoff, tracker.pdim, made or tracker.job
         pproc, post, pfoff, pdim = tracker.pproc, tracker.post, tracker.pfoff, tracker.pdim
         key = ('pitch', rate)
@@ -1569,11 +1734,18 @@ def _extract_features_by_stage(config, utterances, warps, log, tolerance=2):
         if 'pitch' in config:
             params = {k: v for k, v in config['pitch'].items()
                       if k not in ('processor', 'postprocessing')}
-            params['sample_rate'] = rate
             params['frame_shift'] = frame_shift
             params['frame_length'] = frame_length
-            raw = _processor_class('kaldi_pitch')(**params)._process_batch(group)
-            post = _processor_class('kaldi_pitch_post')(
+            pitch_name, post_name = _pitch_processors(config)
+            if pitch_name == 'crepe_pitch':   # (works at 16 kHz whatever the audio: the public processors)
+                tracker = _processor_class(pitch_name)(**params)
+                if rate != tracker.sample_rate:
+                    tracker.resample = 'kaldi'   # (the resampler of the device-resident path, and its properties)
+                raw = tracker._process_batch(group, names=[utts[i].name for i in idx])
+            else:
+                params['sample_rate'] = rate
+                raw = _processor_class(pitch_name)(**params)._process_batch(group)
+            post = _processor_class(post_name)(
                 **config['pitch']['postprocessing'])._process_batch(raw)
             for i, p in zip(idx, post):
                 pitch[i] = p

@@ -20,6 +20,12 @@ per rate in one launch, straight into the batch's 16 kHz block; the samples are 
 the resampling (after it on the default path) and the resampled length is Kaldi's.  The resampling of the
 output rows to the row count (``scipy.signal.resample``, on the host) is another operation and stays as it is.
 
+The pipeline's CREPE pitch entry (:mod:`shennong_amd.pipeline`) keeps everything after the decoder on the device
+as well: :meth:`CrepeBatch.rows` (``snf_crepe_rows``: that row resampling and the clamp) and
+:meth:`CrepeBatch.convert` (``snf_crepe_voicing_convert``: :func:`predict_voicing`, the interpolation and
+:func:`pov_to_nccf` of :class:`CrepePitchPostProcessor`), ``kernels_crepe_tail.hip``.  The two processors below
+keep their host tail.
+
 Weights: the five pretrained models are not shipped with this package.  ``model-<capacity>.npz`` is looked up
 in the directory named by the environment variable ``SHENNONG_AMD_CREPE_DIR`` and then in
 ``shennong_amd/share/crepe/``; ``tools/convert_crepe_h5.py`` writes that file from the published Keras
@@ -243,7 +249,8 @@ def _off(a):
 
 class CrepeBatch:
     """The stages of one batch of 16 kHz int16 utterances on the device, each one call through the C ABI:
-    :meth:`forward` then :meth:`decode` (the tests and ``tools/time_crepe.py`` read the intermediate buffers)"""
+    :meth:`forward` then :meth:`decode` (the tests and ``tools/time_crepe.py`` read the intermediate buffers),
+    and the tail that stays on the device, :meth:`rows` then :meth:`convert` (the pipeline's CREPE entry)"""
 
     def __init__(self, waves, hop, center=True, device=None):
         device = _backend.get_device() if device is None else int(device)
@@ -251,6 +258,7 @@ class CrepeBatch:
         soff = np.zeros(len(waves) + 1, dtype=np.int64)
         np.cumsum([w.shape[0] for w in waves], out=soff[1:])
         self._layout(_backend.upload_rows(waves, np.int16, device), soff, hop, center, device)
+        self._owns_wave = True
 
     @classmethod
     def from_device(cls, block, soff, hop, center=True, device=None):
@@ -259,6 +267,7 @@ class CrepeBatch:
         batch = cls.__new__(cls)
         batch._layout(block, np.ascontiguousarray(soff, dtype=np.int64), hop, center,
                       block.device if device is None else device)
+        batch._owns_wave = False   # (the caller's block)
         return batch
 
     def _layout(self, block, soff, hop, center, device):
@@ -270,7 +279,7 @@ class CrepeBatch:
         np.cumsum(self.frames, out=self.foff[1:])
         self.total_frames = int(self.foff[-1])
         self.wave = block
-        self.activation = self.out = self.bins = None
+        self.activation = self.out = self.bins = self.resampled = self.nccf_pitch = None
 
     def forward(self, model, precision='float32'):
         """The activation [total_frames, 360] float32 stays on the device.  `precision` 'bfloat16': blocks 2 to 6
@@ -298,19 +307,135 @@ class CrepeBatch:
     def host_activation(self):
         return self.activation.download(np.empty((self.total_frames, _BINS), dtype=np.float32))
 
-    def decode(self, viterbi=True):
-        """(confidence, Hertz) per frame [total_frames, 2] float64 (host)"""
+    def decode(self, viterbi=True, resident=False):
+        """(confidence, Hertz) per frame [total_frames, 2] float64 (host); with `resident` nothing comes down
+        (None): the rows stay on the device for :meth:`rows`"""
         tables = _device_tables(self.device)
         self.out = _backend.DeviceBuffer(max(16, 16 * self.total_frames), self.device)
         self.bins = _backend.DeviceBuffer(max(16, 8 * self.total_frames), self.device)
         _backend.check(_backend.lib().snf_crepe_decode(
             self.device, _p(self.activation), _off(self.foff), self.n, int(bool(viterbi)), _p(tables), _p(self.out),
             _p(self.bins), None))
+        if resident:
+            return None
         return self.out.download(np.empty((self.total_frames, 2), dtype=np.float64))
 
     def host_bins(self):
         """(first argmax, decoded bin) per frame, [2, total_frames] int32"""
         return self.bins.download(np.empty((2, self.total_frames), dtype=np.int32))
+
+    # ---- the tail: decoder -> rows -> (NCCF, pitch), everything on the device -------------------------------
+    def rows(self, out_counts):
+        """The decoder's (confidence, Hertz) rows, which stay on the device (``decode(resident=True)``),
+        resampled per utterance to `out_counts` rows by the Fourier method, confidence clamped
+        (``snf_crepe_rows``); read them with :meth:`host_rows`"""
+        counts = np.ascontiguousarray(out_counts, dtype=np.int64).reshape(-1)
+        if counts.shape[0] != self.n:
+            raise ValueError(f'{self.n} utterances, {counts.shape[0]} row counts')
+        roff = np.zeros(self.n + 1, dtype=np.int64)
+        np.cumsum(counts, out=roff[1:])
+        if self.out is None:
+            raise ValueError('rows: nothing decoded yet')
+        resampled = _backend.DeviceBuffer(max(16, 16 * int(roff[-1])), self.device)
+        try:
+            _backend.check(_backend.lib().snf_crepe_rows(
+                self.device, _p(self.out), _off(self.foff), _off(roff), self.n, _p(resampled), None))
+        except BaseException:
+            resampled.free()
+            raise
+        old, self.resampled = self.resampled, resampled
+        if old is not None and old is not self.out:   # (the rows of an earlier call; set_rows' block is `out` too)
+            old.free(synced=True)                     # (that call returned: its stream is synchronised)
+        self.roff, self.total_rows = roff, int(roff[-1])
+
+    def set_rows(self, rows, offsets):
+        """Replaces the decoder's output by the host matrix `rows` [total, 2] float64, utterance u being the
+        rows ``offsets[u]:offsets[u + 1]``: both as the input of :meth:`rows` and as its result (the tail's
+        kernels alone, no network)"""
+        rows = np.ascontiguousarray(rows, dtype=np.float64)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if rows.ndim != 2 or rows.shape[1] != 2 or offsets.shape[0] != self.n + 1 or offsets[-1] != rows.shape[0]:
+            raise ValueError(f'rows must have shape [total, 2] and {self.n + 1} offsets that end at total')
+        self.foff, self.total_frames = offsets, int(offsets[-1])
+        self.frames = np.diff(offsets)
+        uploaded = _backend.DeviceBuffer(max(16, rows.nbytes), self.device)
+        uploaded.upload(rows)
+        replaced = {id(b): b for b in (self.out, self.resampled) if b is not None}
+        self.out = self.resampled = uploaded
+        for block in replaced.values():
+            block.free(synced=True)   # (the calls that used them returned: their streams are synchronised)
+        self.roff, self.total_rows = offsets, self.total_frames
+
+    def host_rows(self):
+        """The rows :meth:`rows` made, [total_rows, 2] float64"""
+        return self.resampled.download(np.empty((self.total_rows, 2), dtype=np.float64))
+
+    def convert(self):
+        """The (NCCF, pitch) float32 rows the Kaldi post-processing takes, from the rows of :meth:`rows`
+        (``snf_crepe_voicing_convert``): they stay on the device (:attr:`nccf_pitch`, :meth:`host_nccf_pitch`),
+        the status of every utterance comes down and the first that is not 0 raises what
+        :class:`CrepePitchPostProcessor` raises for such an utterance"""
+        if getattr(self, 'resampled', None) is None:
+            raise ValueError('convert: no rows yet')
+        nccf_pitch = _backend.DeviceBuffer(max(16, 8 * self.total_rows), self.device)
+        status = _backend.DeviceBuffer(max(16, 4 * self.n), self.device)
+        try:
+            model = voicing_model()
+            _backend.check(_backend.lib().snf_crepe_voicing_convert(
+                self.device, _p(self.resampled), _off(self.roff), self.n,
+                model.ctypes.data_as(C.POINTER(C.c_double)), _p(nccf_pitch), _p(status), None))
+            self.status = status.download(np.empty(self.n, dtype=np.int32))
+        except BaseException:
+            nccf_pitch.free()
+            raise
+        finally:
+            status.free()
+        old, self.nccf_pitch = getattr(self, 'nccf_pitch', None), nccf_pitch
+        if old is not None:
+            old.free(synced=True)
+        _raise_for_status(self.status)
+
+    def host_nccf_pitch(self):
+        """The rows :meth:`convert` made, [total_rows, 2] float32"""
+        return self.nccf_pitch.download(np.empty((self.total_rows, 2), dtype=np.float32))
+
+    def release(self, synced=False):
+        """Gives the batch's device blocks back - the audio too when the batch uploaded it itself, not when it
+        is the caller's (:meth:`from_device`).  `synced`: every call that used them has returned, and each
+        waits for its stream (see ``DeviceBuffer.free``)"""
+        names = ('activation', 'out', 'bins', 'resampled', 'nccf_pitch')
+        for name in names + (('wave',) if getattr(self, '_owns_wave', False) else ()):
+            block = getattr(self, name, None)
+            setattr(self, name, None)
+            if block is not None:
+                block.free(synced=synced)   # (a second free of a block held under two names is a no-op)
+
+
+_STATUS_MESSAGES = {
+    1: 'No voiced frames',
+    2: 'Not all pitch values are positive: issue with extracted pitch or interpolation',
+    3: 'f(a) and f(b) must have different signs'}
+
+
+def _raise_for_status(status):
+    """The exception of the first utterance whose status (``snf_crepe_voicing_convert``) is not 0: the texts of
+    :meth:`CrepePitchPostProcessor._convert` and :func:`pov_to_nccf`"""
+    for code in np.asarray(status).reshape(-1).tolist():
+        if code:
+            if code not in _STATUS_MESSAGES:
+                raise RuntimeError(f'crepe conversion: unknown status {code}')
+            raise ValueError(_STATUS_MESSAGES[code])
+
+
+def voicing_model():
+    """The float64 model ``snf_crepe_voicing_convert`` takes, with the values :func:`predict_voicing` and
+    :func:`pov_to_nccf` compute: log(2 pi variance), the two means, the variance, log start, the log transition
+    matrix by rows, then the range of the NCCF -> POV map"""
+    variance = 0.25
+    log_transition = np.log(np.array([[0.99, 0.01], [0.01, 0.99]]))
+    return np.ascontiguousarray(np.concatenate([
+        [np.log(2 * np.pi * variance), 0.0, 1.0, variance, np.log(0.5)], log_transition.reshape(-1),
+        [_nccf_to_pov(0.0), _nccf_to_pov(1.0)]]), dtype=np.float64)
 
 
 def _to_bf16_bits(a):

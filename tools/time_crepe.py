@@ -7,8 +7,16 @@ utterances and scaled to the batch (--host-utts 0 leaves it out).  One JSON line
 (profiles/crepe_timing.jsonl; profiles/crepe_bf16_timing.jsonl for --precision float32 bfloat16: both in one
 process on the same inputs, each after its own warm-up, the later lines with their gain over float32).
 
+With --tail, one line instead (profiles/crepe_tail_timing.jsonl; 1 000 utterances of 3 s there): from the
+activation to the post-processed pitch on the host, the host tail (decoder, download, scipy.signal.resample,
+predict_voicing, np.interp, pov_to_nccf per utterance, then the Kaldi post-processing kernel: what
+CrepePitchProcessor and CrepePitchPostProcessor do) against the device tail (decoder, snf_crepe_rows,
+snf_crepe_voicing_convert, the same post-processing kernel, one download), best of 3 in the same process, and
+extract_features with the CREPE pitch entry on the same corpus, host to host.
+
     python tools/time_crepe.py [--utts 100] [--seconds 3] [--capacities tiny,full] [--host-utts 1]
                                [--precision float32 [bfloat16]]
+    python tools/time_crepe.py --tail --utts 1000 --capacities tiny
 """
 
 import argparse
@@ -43,6 +51,60 @@ def best_of(n, call):
     return best
 
 
+def tail_line(args, waves, utterances, capacity):
+    """The tail alone, host against device, and the pipeline with the CREPE entry"""
+    import scipy.signal
+    from shennong_amd import Features, _backend, pipeline
+    from shennong_amd.processor import CrepePitchPostProcessor, CrepePitchProcessor, pitch_crepe
+    proc = CrepePitchProcessor(model_capacity=capacity)
+    post = CrepePitchPostProcessor(delta_pitch_noise_stddev=0)
+    model = pitch_crepe.device_model(capacity, _backend.get_device())
+    batch = pitch_crepe.CrepeBatch(waves, 160, True)
+    batch.forward(model)
+    counts = np.asarray([proc._output_rows(len(w)) for w in waves], dtype=np.int64)
+    roff = np.concatenate([[0], np.cumsum(counts)])
+    qplan = _backend.get_plan(post._build_options())
+    pdim = qplan.post_ndims(2)
+
+    def host_tail():
+        raw = batch.decode(True)
+        feats, properties = [], proc.get_properties()
+        for a, b, m in zip(batch.foff[:-1], batch.foff[1:], counts):
+            data = scipy.signal.resample(raw[a:b], m)
+            data[data[:, 0] < 1e-2, 0] = 0
+            data[data[:, 0] > 1, 0] = 1
+            feats.append(Features(data, proc.times(m), properties=properties))
+        return np.concatenate([f.data for f in post._process_batch(feats)])
+
+    def device_tail():
+        batch.decode(True, resident=True)
+        batch.rows(counts)
+        batch.convert()
+        d_pitch = _backend.DeviceBuffer(int(roff[-1]) * pdim * 4)
+        qplan.run_post_device(batch.nccf_pitch.ptr, 2, roff, d_pitch.ptr, noise_call=1)
+        out = d_pitch.download(np.empty((int(roff[-1]), pdim), dtype=np.float32))
+        for block in (d_pitch, batch.resampled, batch.nccf_pitch):
+            block.free(synced=True)
+        return out
+
+    want, got = host_tail(), device_tail()   # (warm-up, and the two results side by side)
+    host = best_of(3, host_tail)
+    device = best_of(3, device_tail)
+    config = pipeline.get_default_config('mfcc', with_delta=True)
+    config['mfcc']['dither'] = 0
+    config['pitch'] = pipeline.get_crepe_pitch_config()
+    config['pitch']['model_capacity'] = capacity
+    config['pitch']['postprocessing']['delta_pitch_noise_stddev'] = 0
+    pipeline.extract_features(config, utterances)
+    whole = best_of(3, lambda: pipeline.extract_features(config, utterances))
+    return {
+        'what': 'crepe tail', 'capacity': capacity, 'device': _backend.device_name(), 'utts': args.utts,
+        'seconds_each': args.seconds, 'frames': batch.total_frames, 'rows': int(roff[-1]),
+        'host_tail_s': round(host, 5), 'device_tail_s': round(device, 5), 'ratio_host_over_device': round(host / device, 1),
+        'max_abs_difference': float(np.abs(want.astype(np.float64) - got).max()),
+        'extract_features_crepe_s': round(whole, 5), 'host_cpus': len(os.sched_getaffinity(0))}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--utts', type=int, default=100)
@@ -50,6 +112,7 @@ def main():
     ap.add_argument('--capacities', default='tiny,full')
     ap.add_argument('--host-utts', type=int, default=1)
     ap.add_argument('--precision', nargs='+', default=['float32'], choices=['float32', 'bfloat16'])
+    ap.add_argument('--tail', action='store_true')
     args = ap.parse_args()
 
     import crepe_f64 as f64
@@ -66,6 +129,9 @@ def main():
             weights = f64.make_weights(capacity, 40)
             np.savez(os.path.join(directory, 'model-%s.npz' % capacity),
                      **{k: v.astype(np.float32) for k, v in weights.items()})
+            if args.tail:
+                print(json.dumps(tail_line(args, waves, utterances, capacity)), flush=True)
+                continue
             proc = CrepePitchProcessor(model_capacity=capacity)
             model = pitch_crepe.device_model(capacity, _backend.get_device())
             batch = pitch_crepe.CrepeBatch(waves, 160, True)
