@@ -493,6 +493,36 @@ int snf_dense_layer_bf16(int device_id, const float* d_x, int64_t m, int32_t k, 
 int snf_bottleneck_forward_bf16(int device_id, const float* d_x, const int64_t* h_row_offsets, int64_t n_utts,
                                 const int32_t* h_widths, const void* const* h_params, float* d_bn, float* d_out,
                                 void* stream);
+/* The whole extractor in one call (reference bottleneck.py:670-764 BottleneckProcessor.process from the VAD on:
+ * _compute_vad, _add_dither, _fbank_htk, the voiced mean, _preprocess_nn_input, _create_nn_extract_st_BN): from
+ * the resident 8 kHz int16 block d_wave to the float32 feature rows, what snf_bottleneck_vad, _fbank, _nn_input
+ * and _forward (bf16 != 0: _forward_bf16, h_params[2], [4], [8], [10] packed images) give when called one after
+ * the other on the same input - bit for bit, for any scratch_bytes, dither included (keyed per utterance and
+ * sample as there).  Everything is enqueued on one stream and waited for once, at the end; nothing comes back to
+ * the host in between (an utterance without voiced frames has a zero mean and gives defined rows).
+ *
+ * Utterance u gives frames + 10 - 2 context rows, written to d_out[. x 80] from row h_out_offsets[u] on;
+ * h_out_offsets[n_utts + 1] (HOST, first >= 0) must leave every utterance at least its rows, and rows of d_out
+ * that belong to no utterance are not touched.  h_status[n_utts] (HOST int32) receives one word per utterance
+ * (bn_status_kernel, after the last layer): bit 0 = no voiced frame, bit 1 = some output value is not finite.
+ *
+ * Bounded scratch: the mask, the voiced counts, the VAD energies, the log-mel energies, the 144-column input, the
+ * first stage and the two hidden buffers live in the calling thread's scratch, none is the caller's.  The batch
+ * is walked in runs of whole consecutive utterances whose intermediates fit scratch_bytes (0 = the default,
+ * 1 GiB): the two hidden buffers take a quarter of the bound each (never less than one tile of 128 rows), the
+ * rest holds the runs' utterances at 105 bytes per frame, 896 per first-stage row, 8 per output row and 104 per
+ * utterance; an utterance that is larger than that runs alone.  Every element depends on its own utterance or
+ * row only, so the cuts do not show in the result.  d_tables, d_basis, h_widths, h_params as in the staged calls. */
+int snf_bottleneck_extract(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                           const float* d_tables, float dither, uint64_t seed, int32_t context, const float* d_basis,
+                           const int32_t* h_widths, const void* const* h_params, int32_t bf16, float* d_out,
+                           const int64_t* h_out_offsets, int32_t* h_status, int64_t scratch_bytes, void* stream);
+/* The runs snf_bottleneck_extract walks for this batch (host only; the loop over the utterances of reference
+ * bottleneck.py:670 process, which takes one signal at a time): returns their number and, when h_run_starts
+ * [n_utts + 1] is given, writes the first utterance of every run followed by n_utts; a negative error code for
+ * arguments the extractor refuses. */
+int64_t snf_bottleneck_extract_runs(const int64_t* h_sample_offsets, int64_t n_utts, int32_t context,
+                                    const int32_t* h_widths, int64_t scratch_bytes, int64_t* h_run_starts);
 
 /* ---- CREPE pitch (reference processor/pitch_crepe.py, CrepePitchProcessor) -------------------------
  * The CREPE network on 16 kHz int16 audio: frames of 1024 samples every `hop`, a signal of n samples gives

@@ -48,7 +48,7 @@ EXPORTS = [
     'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot', 'snf_packed_weights_bf16_size',
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
     'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
-    'snf_crepe_voicing_convert']
+    'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -182,6 +182,10 @@ def lib():
         L.snf_pack_weights_bf16.argtypes = [i32, vp, i32, i32, vp, vp]
         L.snf_dense_layer_bf16.argtypes = [i32, vp, i64, i32, vp, vp, i32, i32, vp, vp]
         L.snf_bottleneck_forward_bf16.argtypes = [i32, vp, pi64, i64, pi32, C.POINTER(vp), vp, vp, vp]
+        L.snf_bottleneck_extract.argtypes = [i32, vp, pi64, i64, vp, f32, C.c_uint64, i32, vp, pi32, C.POINTER(vp),
+                                             i32, vp, pi64, pi32, i64, vp]
+        L.snf_bottleneck_extract_runs.argtypes = [pi64, i64, i32, pi32, i64, pi64]
+        L.snf_bottleneck_extract_runs.restype = i64
         L.snf_crepe_conv.argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, vp]
         L.snf_crepe_forward.argtypes = [i32, vp, pi64, i64, i32, i32, pi32, C.POINTER(vp), vp, vp]
         L.snf_crepe_conv_bf16.argtypes = [i32, vp, i32, i64, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp,

@@ -538,4 +538,209 @@ int snf_bottleneck_forward_bf16(int device_id, const float* d_x, const int64_t* 
   return bn_forward(true, device_id, d_x, h_row_offsets, n_utts, h_widths, h_params, d_bn, d_out, stream);
 }
 
+// ---- the whole extractor in one call ----------------------------------------------------------------------
+namespace {
+constexpr int64_t kBnExtractScratch = int64_t(1) << 30;   // default bound of the intermediates of one run
+constexpr int64_t kBnRunPad = 16 * 256;                   // the 256-byte rounding of a run's pieces
+
+struct BnUtt {
+  int64_t F, R0, R1;   // frames, first-stage rows, output rows
+};
+
+// bytes of one utterance's intermediates: mask, VAD energies, log-mel energies | x, first stage | row map | the
+// voiced mean, the voiced count and the noise word
+int64_t bn_utt_bytes(const BnUtt& t) {
+  return t.F * (1 + 8 + 4 * kBnMel) + t.R0 * 4 * (kBnIn + kBnOut) + t.R1 * 8 + 4 * kBnMel + 4 + 4;
+}
+
+// rows of each of the two hidden buffers: a quarter of the bound each, never less than one tile of 128 rows
+int64_t bn_hidden_rows(int64_t bound, int wmax) {
+  return std::max<int64_t>(128, (bound / 4 / (4 * int64_t(wmax))) & ~int64_t(127));
+}
+
+int bn_extract_check(const int64_t* h_soff, int64_t n_utts, int32_t context, const int32_t* h_widths,
+                     int64_t scratch_bytes, std::vector<BnUtt>* utts) {
+  int rc = bn_check_offsets(h_soff, n_utts, "sample");
+  if (rc) return rc;
+  if (context < 0 || context > bn_max_context())
+    return set_error(SNF_E_INVALID, "bottleneck: context must be in [0, " + std::to_string(bn_max_context()) + "]");
+  if (!h_widths) return set_error(SNF_E_INVALID, "bottleneck: null layer description");
+  for (int i = 0; i < 4; ++i)
+    if (h_widths[i] < 1 || h_widths[i] > (1 << 20))
+      return set_error(SNF_E_INVALID, "bottleneck: layer width " + std::to_string(i) + " out of range");
+  if (scratch_bytes < 0) return set_error(SNF_E_INVALID, "bottleneck: scratch_bytes < 0");
+  const int span = kBnStackStep * (kBnStack - 1);
+  utts->resize(n_utts);
+  for (int64_t u = 0; u < n_utts; ++u) {
+    const int64_t F = bn_frames(h_soff[u + 1] - h_soff[u]), rows = F + 2 * kBnEdge - 2 * context;
+    if (F < 1 || rows < 1)
+      return set_error(SNF_E_INVALID, "bottleneck: utterance " + std::to_string(u) + " has " + std::to_string(F) +
+                                          " frames, too few for one row at context " + std::to_string(context));
+    if (rows <= span)
+      return set_error(SNF_E_INVALID, "bottleneck: utterance " + std::to_string(u) + " has " + std::to_string(rows) +
+                                          " first-stage rows, the stack needs more than " + std::to_string(span));
+    (*utts)[u] = {F, rows, rows - span};
+  }
+  return SNF_OK;
+}
+
+// runs of whole consecutive utterances whose intermediates fit the bound beside the two hidden buffers (an
+// utterance that does not fit runs alone): run r is the utterances start[r] .. start[r + 1]
+void bn_extract_runs(const std::vector<BnUtt>& utts, const int32_t* h_widths, int64_t scratch_bytes,
+                     std::vector<int64_t>* start, int64_t* hidden_rows) {
+  const int wmax = std::max(std::max(h_widths[0], h_widths[1]), std::max(h_widths[2], h_widths[3]));
+  const int64_t bound = scratch_bytes > 0 ? scratch_bytes : kBnExtractScratch;
+  *hidden_rows = bn_hidden_rows(bound, wmax);
+  const int64_t room = bound - 2 * *hidden_rows * wmax * 4 - kBnRunPad;
+  const int64_t n = static_cast<int64_t>(utts.size());
+  start->assign(1, 0);
+  int64_t held = 0;
+  for (int64_t u = 0; u < n; ++u) {
+    const int64_t c = bn_utt_bytes(utts[u]);
+    if (u > start->back() && held + c > room) {
+      start->push_back(u);
+      held = 0;
+    }
+    held += c;
+  }
+  if (n > 0) start->push_back(n);
+}
+}  // namespace
+
+int64_t snf_bottleneck_extract_runs(const int64_t* h_sample_offsets, int64_t n_utts, int32_t context,
+                                    const int32_t* h_widths, int64_t scratch_bytes, int64_t* h_run_starts) {
+  std::vector<BnUtt> utts;
+  int rc = bn_extract_check(h_sample_offsets, n_utts, context, h_widths, scratch_bytes, &utts);
+  if (rc) return rc;
+  std::vector<int64_t> start;
+  int64_t hidden_rows = 0;
+  bn_extract_runs(utts, h_widths, scratch_bytes, &start, &hidden_rows);
+  if (h_run_starts) std::copy(start.begin(), start.end(), h_run_starts);
+  return start.empty() ? 0 : static_cast<int64_t>(start.size()) - 1;
+}
+
+int snf_bottleneck_extract(int device_id, const int16_t* d_wave, const int64_t* h_sample_offsets, int64_t n_utts,
+                           const float* d_tables, float dither, uint64_t seed, int32_t context, const float* d_basis,
+                           const int32_t* h_widths, const void* const* h_params, int32_t bf16, float* d_out,
+                           const int64_t* h_out_offsets, int32_t* h_status, int64_t scratch_bytes, void* stream) {
+  std::vector<BnUtt> utts;
+  int rc = bn_extract_check(h_sample_offsets, n_utts, context, h_widths, scratch_bytes, &utts);
+  if (rc) return rc;
+  if (!(dither >= 0.0f)) return set_error(SNF_E_INVALID, "bottleneck: dither must be >= 0");
+  if (!h_params) return set_error(SNF_E_INVALID, "bottleneck: null layer description");
+  for (int i = 0; i < 12; ++i)
+    if (!h_params[i]) return set_error(SNF_E_INVALID, "bottleneck: null parameter buffer " + std::to_string(i));
+  if (bf16)
+    for (int i : {2, 4, 8, 10})
+      if (reinterpret_cast<uintptr_t>(h_params[i]) & 15)
+        return set_error(SNF_E_INVALID, "bottleneck: packed weights " + std::to_string(i) + " are not 16-byte aligned");
+  if (n_utts == 0) return SNF_OK;
+  if (!d_wave || !d_tables || !d_basis || !d_out || !h_status) return set_error(SNF_E_INVALID, "bottleneck: null buffer");
+  if (reinterpret_cast<uintptr_t>(d_tables) & 7) return set_error(SNF_E_INVALID, "bottleneck: tables are not 8-byte aligned");
+  if (!h_out_offsets) return set_error(SNF_E_INVALID, "bottleneck: null output offsets table");
+  if (h_out_offsets[0] < 0) return set_error(SNF_E_INVALID, "bottleneck: output offsets must not be negative");
+  for (int64_t u = 0; u < n_utts; ++u)
+    if (h_out_offsets[u + 1] - h_out_offsets[u] < utts[u].R1)
+      return set_error(SNF_E_INVALID, "bottleneck: output offsets leave utterance " + std::to_string(u) +
+                                          " fewer than its " + std::to_string(utts[u].R1) + " rows");
+  if (h_out_offsets[n_utts] > (int64_t(1) << 40)) return set_error(SNF_E_INVALID, "bottleneck: batch too large");
+
+  std::vector<int64_t> start;
+  int64_t hidden_rows = 0;
+  bn_extract_runs(utts, h_widths, scratch_bytes, &start, &hidden_rows);
+  const int64_t n_runs = static_cast<int64_t>(start.size()) - 1;
+  // one table blob: sample offsets | output starts | per run its own frame, first-stage and output offsets from 0
+  std::vector<int64_t> tab(h_sample_offsets, h_sample_offsets + n_utts + 1);
+  tab.insert(tab.end(), h_out_offsets, h_out_offsets + n_utts + 1);
+  std::vector<int64_t> at(n_runs);
+  int64_t max_f = 1, max_r0 = 1, max_r1 = 1, max_nu = 1;
+  for (int64_t r = 0; r < n_runs; ++r) {
+    const int64_t u0 = start[r], nu = start[r + 1] - u0;
+    at[r] = static_cast<int64_t>(tab.size());
+    tab.resize(tab.size() + 3 * (nu + 1), 0);
+    int64_t* foff = tab.data() + at[r];
+    int64_t *roff = foff + nu + 1, *ooff = roff + nu + 1;
+    for (int64_t u = 0; u < nu; ++u) {
+      foff[u + 1] = foff[u] + utts[u0 + u].F;
+      roff[u + 1] = roff[u] + utts[u0 + u].R0;
+      ooff[u + 1] = ooff[u] + utts[u0 + u].R1;
+    }
+    max_f = std::max(max_f, foff[nu]);
+    max_r0 = std::max(max_r0, roff[nu]);
+    max_r1 = std::max(max_r1, ooff[nu]);
+    max_nu = std::max(max_nu, nu);
+  }
+  const int wmax = std::max(std::max(h_widths[0], h_widths[1]), std::max(h_widths[2], h_widths[3]));
+  const int64_t chunk = std::min(hidden_rows, (max_r0 + 127) & ~int64_t(127));
+  Planless lay;
+  auto d_tab = lay.take<int64_t>(tab.size());
+  auto d_status = lay.take<int32_t>(n_utts);
+  auto mask = lay.take<uint8_t>(max_f);
+  auto voiced = lay.take<int32_t>(max_nu);
+  auto energy = lay.take<double>(max_f);
+  auto logmel = lay.take<float>(kBnMel * max_f);
+  auto utt_noise = lay.take<uint32_t>(max_nu);
+  auto mean = lay.take<float>(kBnMel * max_nu);
+  auto x = lay.take<float>(kBnIn * max_r0);
+  auto bn = lay.take<float>(kBnOut * max_r0);
+  auto d_map = lay.take<int64_t>(max_r1);
+  auto h1 = lay.take<float>(chunk * wmax);
+  auto h2 = lay.take<float>(chunk * wmax);
+  if ((rc = lay.begin(device_id, stream))) return rc;
+  SNF_HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice, lay.s));
+  const int64_t* d_soff = d_tab;
+  const int64_t* d_ostart = d_soff + n_utts + 1;
+  const void* const* P = h_params;
+  auto F = [](const void* p) { return static_cast<const float*>(p); };
+  auto hidden = [&](const float* a, int64_t m, int k, int i, int n, int act, float* y) {
+    return bf16 ? launch_bn_dense_bf16(a, m, k, static_cast<const uint16_t*>(P[i]), F(P[i + 1]), n, act, y, lay.s)
+                : launch_bn_dense(a, m, k, F(P[i]), F(P[i + 1]), n, act, y, nullptr, 0, 0, lay.s);
+  };
+  for (int64_t r = 0; r < n_runs && !rc; ++r) {
+    const int64_t u0 = start[r], nu = start[r + 1] - u0;
+    const int64_t* h_ooff = tab.data() + at[r] + 2 * (nu + 1);
+    const int64_t* d_foff = d_tab + at[r];
+    const int64_t *d_roff = d_foff + nu + 1, *d_ooff = d_roff + nu + 1;
+    const int64_t total_f = tab[at[r] + nu], R0 = tab[at[r] + 2 * nu + 1], R1 = h_ooff[nu];
+    rc = launch_bn_vad(d_wave, d_soff + u0, d_foff, nu, energy, mask, voiced, lay.s);
+    if (!rc)
+      rc = launch_bn_fbank(d_wave, d_soff + u0, d_foff, nu, total_f, d_tables, dither, seed, utt_noise, logmel, lay.s);
+    if (!rc) rc = launch_bn_nn_input(logmel, mask, voiced, d_foff, d_roff, nu, R0, context, d_basis, mean, x, lay.s);
+    if (!rc) rc = launch_bn_row_map(d_roff, d_ooff, nu, R1, d_map, lay.s);
+    for (int64_t a = 0; a < R0 && !rc; a += chunk) {
+      const int64_t m = std::min(chunk, R0 - a);
+      float* xa = x;
+      float* ba = bn;
+      rc = launch_bn_dense(xa + a * kBnIn, m, kBnIn, F(P[0]), F(P[1]), h_widths[0], 1, h1, nullptr, 0, 0, lay.s);
+      if (!rc) rc = hidden(h1, m, h_widths[0], 2, h_widths[1], 1, h2);
+      if (!rc) rc = hidden(h2, m, h_widths[1], 4, kBnOut, 0, ba + a * kBnOut);
+    }
+    int64_t u = 0;   // the utterance of the run that holds the next output row
+    for (int64_t a = 0; a < R1 && !rc; a += chunk) {
+      const int64_t m = std::min(chunk, R1 - a);
+      const int64_t* map = d_map;
+      float* h2p = h2;
+      rc = launch_bn_dense(bn, m, kBnStack * kBnOut, F(P[6]), F(P[7]), h_widths[2], 1, h1, map + a, kBnOut,
+                           kBnStackStep, lay.s);
+      if (!rc) rc = hidden(h1, m, h_widths[2], 8, h_widths[3], 1, h2);
+      // the last layer writes where the caller wants the rows: one launch per stretch of utterances whose rows
+      // follow each other in d_out (a row's value does not depend on the rows beside it)
+      for (int64_t p = a; p < a + m && !rc;) {
+        while (h_ooff[u + 1] <= p) ++u;
+        int64_t dest = h_out_offsets[u0 + u] + (p - h_ooff[u]), v = u, q = std::min(a + m, h_ooff[u + 1]);
+        while (q < a + m && h_out_offsets[u0 + v + 1] == h_out_offsets[u0 + v] + utts[u0 + v].R1) {
+          ++v;
+          q = std::min(a + m, h_ooff[v + 1]);
+        }
+        rc = hidden(h2p + (p - a) * h_widths[3], q - p, h_widths[3], 10, kBnOut, 0, d_out + dest * kBnOut);
+        p = q;
+      }
+    }
+    if (!rc) rc = launch_bn_status(voiced, d_out, d_ostart + u0, d_ooff, nu, static_cast<int32_t*>(d_status) + u0, lay.s);
+  }
+  if (!rc && hipMemcpyAsync(h_status, d_status, sizeof(int32_t) * n_utts, hipMemcpyDeviceToHost, lay.s) != hipSuccess)
+    rc = set_error(SNF_E_HIP, "bottleneck extract: copy of the status failed");
+  return lay.finish(rc, "bottleneck extract kernels failed");
+}
+
 }  // extern "C"

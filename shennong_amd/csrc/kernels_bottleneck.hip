@@ -49,6 +49,11 @@
 // VAD (bn_vad_kernel): one workgroup per utterance.  int16-wrapped squares summed per frame in int64,
 // then float64 throughout: standardisation and five EM passes of the 1-D 3-component GMM, every sum a
 // fixed-order reduction (strided partials ascending, then a binary tree in LDS).  No atomics.
+//
+// Status (bn_status_kernel, the last launch of snf_bottleneck_extract): one workgroup per utterance reads the
+// voiced count and the utterance's output rows where the last layer put them and writes one word - bit 0 no voiced
+// frame, bit 1 a value that is not finite - so that the one-call extractor needs no host round trip between its
+// stages: the host reads the words after the call's only wait.
 #include <math.h>
 
 #include "snf_internal.h"
@@ -609,9 +614,44 @@ __global__ void __launch_bounds__(kThreads) bn_nn_input_kernel(const float* __re
   for (int j = 0; j < kBases; ++j) dst[j] = acc[j];
 }
 
+// ---- status word of the one-call extractor --------------------------------------------------------------
+// status[u] = (voiced[u] == 0) | 2 (some value of the utterance's output rows is not finite).  One workgroup per
+// utterance; rows out_start[u] .. + (ooff[u + 1] - ooff[u]) of `out`.  Each wave folds its lanes' flags with one
+// ballot, the four waves meet in LDS and one lane stores the word: no atomics.
+__global__ void __launch_bounds__(kThreads) bn_status_kernel(const int32_t* __restrict__ voiced,
+                                                            const float* __restrict__ out,
+                                                            const int64_t* __restrict__ out_start,
+                                                            const int64_t* __restrict__ ooff,
+                                                            int32_t* __restrict__ status) {
+  __shared__ int wave_bad[kThreads / 64];
+  const int64_t u = blockIdx.x;
+  const int64_t n = (ooff[u + 1] - ooff[u]) * 80;
+  const float* src = out + out_start[u] * 80;
+  bool bad = false;
+  for (int64_t i = threadIdx.x; i < n; i += kThreads) bad = bad || !isfinite(src[i]);
+  const bool any = __ballot(bad) != 0ull;
+  if ((threadIdx.x & 63) == 0) wave_bad[threadIdx.x >> 6] = any ? 1 : 0;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int b = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) b |= wave_bad[w];
+    status[u] = (voiced[u] == 0 ? 1 : 0) | (b ? 2 : 0);
+  }
+}
+
 unsigned blocks(int64_t n, int64_t per) { return static_cast<unsigned>((n + per - 1) / per); }
 
 }  // namespace
+
+int launch_bn_status(const int32_t* voiced, const float* out, const int64_t* out_start, const int64_t* ooff,
+                     int64_t n_utts, int32_t* status, hipStream_t stream) {
+  if (n_utts <= 0) return SNF_OK;
+  hipLaunchKernelGGL(bn_status_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(kThreads), 0, stream, voiced, out,
+                     out_start, ooff, status);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
 
 int bn_table_floats() { return kWin + 2 * kFft + kBins * kMel; }
 int bn_max_context() { return kMaxContext; }

@@ -83,7 +83,7 @@ ThreadScratch* thread_scratch(int device_id);
 // address come from the same line.  finish() waits for the stream, so the scratch is free again for the thread's
 // next call.
 struct Planless {
-  static constexpr int kMaxPieces = 8;
+  static constexpr int kMaxPieces = 16;
   size_t total = 0, offset[kMaxPieces];
   char* base = nullptr;
   hipStream_t s = nullptr;

@@ -433,6 +433,9 @@ int launch_bn_vad(const int16_t* wave, const int64_t* soff, const int64_t* foff,
 int launch_bn_nn_input(const float* logmel, const uint8_t* mask, const int32_t* voiced, const int64_t* foff,
                        const int64_t* roff, int64_t n_utts, int64_t total_rows, int context, const float* hd,
                        float* mean, float* x, hipStream_t stream);
+// status[u] = (voiced[u] == 0) | 2 (a non-finite value in rows out_start[u] .. + ooff[u + 1] - ooff[u] of out[. x 80])
+int launch_bn_status(const int32_t* voiced, const float* out, const int64_t* out_start, const int64_t* ooff,
+                     int64_t n_utts, int32_t* status, hipStream_t stream);
 
 // CREPE pitch kernels (kernels_crepe.hip): see that file's header for the design
 constexpr int kConvNorm = 1, kConvPool = 2, kConvSigmoid = 4;   // epilogue of launch_crepe_conv

@@ -28,8 +28,18 @@ the host's Fourier method - in the streamed second pass and for pinned corpora t
 and the pitch properties record it as ``resample: 'kaldi'``, exactly as a
 :class:`~shennong_amd.processor.pitch_crepe.CrepePitchProcessor` with ``resample = 'kaldi'`` does.
 
-Not provided by this pipeline: bottleneck features (the processor exists -
-:class:`shennong_amd.processor.bottleneck.BottleneckProcessor` - but is not a pipeline entry yet).
+A 'bottleneck' entry (:func:`get_bottleneck_config` writes it; ``get_default_config('bottleneck')`` does not, and
+:func:`valid_features` keeps to the four Kaldi-style families) is the one features entry of its configuration, with
+pitch, CMVN and delta behind it like any other.  The extractor works on 8 kHz int16 audio, so the audio stage brings
+every group of another rate there first, on the device (Kaldi's ResampleWaveform on the int16 samples,
+``_backend.resample_device``), and the 8 kHz block takes the place of the group's audio: energy / VAD, the pitch
+tracker and the extractor all read it, ``properties['audio']['sample_rate']`` is 8000 (reference
+pipeline_manager.py:228-245) and the 'bottleneck' properties of the utterances that were at another rate record
+``resample: 'kaldi'``.  The features are ONE call, ``snf_bottleneck_extract``
+(:meth:`shennong_amd.processor.bottleneck.BottleneckBatch.extract`): VAD, front end, context projection and both
+networks on one stream, the intermediates in bounded scratch, the rows written straight into the group's features
+block, and one status word per utterance (no voiced frame / a value that is not finite) that is turned into the
+processor's exceptions after the call.  VTLN is refused, as in the reference.
 """
 
 import os
@@ -48,6 +58,7 @@ from shennong_amd.utils import copy_properties, get_njobs
 
 
 _PROCESSORS = {
+    'bottleneck': ('processor', 'BottleneckProcessor'),
     'energy': ('processor', 'EnergyProcessor'),
     'filterbank': ('processor', 'FilterbankProcessor'),
     'mfcc': ('processor', 'MfccProcessor'),
@@ -66,6 +77,17 @@ _PROCESSORS = {
 def valid_features():
     """The main features the pipeline can extract (post-processing excluded)"""
     return ['spectrogram', 'filterbank', 'mfcc', 'plp']
+
+
+def _features_entries():
+    """The entries of a configuration that name its main features: :func:`valid_features` and 'bottleneck' (the
+    reference's list, pipeline_manager.py:20-21)"""
+    return valid_features() + ['bottleneck']
+
+
+def _features_of(config):
+    """The name of the one features entry of a validated configuration"""
+    return [k for k in config.keys() if k in _features_entries()][0]
 
 
 def _processor_class(name):
@@ -89,6 +111,10 @@ def get_default_config(features, to_yaml=False, yaml_commented=True,
     Same dictionary layout as the reference (one entry per processor, parameters with their default
     values, `sample_rate` and `htk_compat` filtered out of the features entry, frame parameters
     filtered out of the pitch entry).
+
+    ``features='bottleneck'`` is refused here.  The pipeline itself does take a bottleneck entry: write the
+    configuration as ``config = {'bottleneck': get_bottleneck_config()}`` and add 'cmvn', 'delta' or 'pitch'
+    entries to it like to any other.
 
     ``with_pitch='crepe'`` is refused here.  The pipeline itself does take a CREPE pitch entry: add one to the
     returned configuration as ``config['pitch'] = get_crepe_pitch_config()``.
@@ -157,6 +183,16 @@ def get_crepe_pitch_config():
             entry[key] = value
     entry['postprocessing'] = _processor_params('crepe_pitch_post')
     return entry
+
+
+def get_bottleneck_config():
+    """The 'bottleneck' entry of a configuration, as the reference's ``get_default_config('bottleneck')`` writes
+    it: the parameters of :class:`~shennong_amd.processor.bottleneck.BottleneckProcessor` with their default
+    values, ``{'weights': 'BabelMulti', 'dither': 0.1}``, read from the constructor's signature - no processor
+    is made, no weights file looked for or loaded.  Use it as ``config = {'bottleneck': get_bottleneck_config()}``."""
+    import inspect
+    signature = inspect.signature(_processor_class('bottleneck').__init__)
+    return {name: p.default for name, p in signature.parameters.items() if name != 'self'}
 
 
 def _pitch_processors(config):
@@ -249,28 +285,36 @@ def _init_config(config, log=get_logger('pipeline', 'warning')):
         except yaml.YAMLError as err:
             raise ValueError(f'error in configuration: {err}') from None
 
-    known = valid_features() + ['cmvn', 'delta', 'pitch', 'vtln', 'bottleneck']
+    known = _features_entries() + ['cmvn', 'delta', 'pitch', 'vtln']
     unknown_keys = [k for k in config.keys() if k not in known]
     if unknown_keys:
         raise ValueError(
             'invalid keys in configuration: {}'.format(', '.join(unknown_keys)))
-    if 'bottleneck' in config:
-        raise ValueError('bottleneck features are not available in this backend')
 
-    features = [k for k in config.keys() if k in valid_features()]
+    features = [k for k in config.keys() if k in _features_entries()]
     if not features:
         raise ValueError(
             'the configuration does not define any features extraction '
             '(must have one and only one entry of {})'
-            .format(', '.join(valid_features())))
+            .format(', '.join(_features_entries())))
     if len(features) > 1:
         raise ValueError(
             'more than one features extraction processors are defined, '
             '(must have one and only one entry of {}): {}'
-            .format(', '.join(valid_features()), ', '.join(features)))
+            .format(', '.join(_features_entries()), ', '.join(features)))
 
-    if 'vtln' in config and features[0] == 'spectrogram':
+    if 'vtln' in config and features[0] in ('spectrogram', 'bottleneck'):
         raise ValueError(f'{features[0]} features do not support VTLN')
+
+    if features[0] == 'bottleneck':
+        # (validated here: its processor is made after the audio is in HBM; a missing weights directory or file
+        # is a RuntimeError there, a name that is not among the files a ValueError)
+        try:
+            _processor_class('bottleneck')(**config['bottleneck'])
+        except RuntimeError as err:
+            raise RuntimeError(f'error in configuration: bottleneck: {err}') from None
+        except (TypeError, ValueError) as err:
+            raise ValueError(f'error in configuration: bottleneck: {err}') from None
 
     if 'cmvn' in config:
         if 'by_speaker' not in config['cmvn']:
@@ -316,8 +360,8 @@ def _init_config(config, log=get_logger('pipeline', 'warning')):
 def _init_warps(warps, config, utterances, log):
     """Per-utterance float warps from warps given by utterance or by speaker
     (reference pipeline.py:496-522)"""
-    features = [k for k in config.keys() if k in valid_features()][0]
-    if features == 'spectrogram':
+    features = _features_of(config)
+    if features in ('spectrogram', 'bottleneck'):
         raise ValueError(f'{features} features do not support VTLN')
     if 'vtln' in config:
         raise ValueError(
@@ -398,13 +442,14 @@ def extract_features(configuration, utterances, warps=None, njobs=1,
     return _extract_features(config, _view_of(utterances), warps, log)
 
 
-def _too_large_for_one_batch(utterances, extra_bytes_per_hour=0):
+def _too_large_for_one_batch(utterances, extra_bytes_per_hour=0, extra_bytes=0):
     """True when one batch over all of `utterances` would need more than half of the HBM that is free
     (_BATCH_BYTES_PER_HOUR per hour of audio while a batch is in flight, plus `extra_bytes_per_hour`: a CREPE
-    pitch entry, :func:`_crepe_bytes_per_hour`)"""
+    pitch entry, :func:`_crepe_bytes_per_hour`, or a bottleneck entry, :func:`_bottleneck_bytes`, which also
+    brings `extra_bytes` whatever the duration: its extractor's bounded scratch)"""
     if _backend.device_count() < 1:   # (host-logic tests with the device pipeline replaced by a stand-in)
         return False
-    need = utterances.duration() / 3600.0 * (_BATCH_BYTES_PER_HOUR + extra_bytes_per_hour)
+    need = utterances.duration() / 3600.0 * (_BATCH_BYTES_PER_HOUR + extra_bytes_per_hour) + extra_bytes
     if need < (8 << 30):              # (no query for what certainly fits)
         return False
     free, _ = _backend.mem_info()
@@ -432,8 +477,8 @@ def extract_features_warp(configuration, utterances, warp, log=get_logger('pipel
     Raises ValueError for an invalid configuration and for spectrogram features (no VTLN there)."""
     get_njobs(njobs, log=log)
     config = _init_config(configuration, log=log)
-    features = [k for k in config.keys() if k in valid_features()][0]
-    if features == 'spectrogram':
+    features = _features_of(config)
+    if features in ('spectrogram', 'bottleneck'):
         raise ValueError(f'{features} features do not support VTLN')
     warps = {utt.name: float(warp) for utt in utterances}
     return _extract_features(config, _view_of(utterances), warps, log, stages=('delta',),
@@ -552,28 +597,53 @@ def _crepe_bytes_per_hour(config):
     one-argument functions keep working for every other configuration)"""
     if 'pitch' not in config or config['pitch'].get('processor', 'kaldi') != 'crepe':
         return 0
-    features = [k for k in config.keys() if k in valid_features()][0]
+    features = _features_of(config)
     shift = float(config[features].get('frame_shift', 0.01))
     return int(round(3600.0 / max(shift, 1.0 / 16000))) * _CREPE_BYTES_PER_FRAME + _CREPE_NATIVE_COPY_PER_HOUR
 
 
+# A bottleneck entry: its features are 80 float32 columns per row, a features block like any other (inside
+# _BATCH_BYTES_PER_HOUR).  On top of that the extractor call holds its intermediates - mask, VAD and log-mel
+# energies, the 144-column input, the first stage, the hidden activations - in the calling thread's scratch, which
+# is BOUNDED: snf_bottleneck_extract walks the batch in runs that fit its default bound of 1 GiB (include/
+# shennong_amd.h), whatever the duration; the whole-batch input (576 bytes per row) and first-stage (320) buffers
+# of BottleneckBatch.forward are never made here.  A group that is not at 8 kHz holds its 8 kHz copy beside the
+# uploaded audio until the resampler has returned, 2 bytes a sample: the rate is not known where the batches are
+# sized, so every hour counts it.
+_BOTTLENECK_SCRATCH_BYTES = 1 << 30
+_BOTTLENECK_NATIVE_COPY_PER_HOUR = 2 * 8000 * 3600
+
+
+def _bottleneck_bytes(config):
+    """(bytes per hour of audio, bytes whatever the duration) a bottleneck entry needs on top of
+    _BATCH_BYTES_PER_HOUR: (0, 0) for any other configuration"""
+    if 'bottleneck' not in config:
+        return 0, 0
+    return _BOTTLENECK_NATIVE_COPY_PER_HOUR, _BOTTLENECK_SCRATCH_BYTES
+
+
 def _sized(estimate, what, config):
     """``estimate(what)`` of :func:`_too_large_for_one_batch` / :func:`default_batch_duration`, with the CREPE
-    entry's bytes per hour when `config` has one"""
-    extra = _crepe_bytes_per_hour(config)
+    entry's bytes per hour when `config` has one and a bottleneck entry's bytes per hour and bounded scratch"""
+    per_hour, fixed = _bottleneck_bytes(config)
+    extra = _crepe_bytes_per_hour(config) + per_hour
+    if fixed:
+        return estimate(what, extra, fixed)
     return estimate(what, extra) if extra else estimate(what)
 
 
-def default_batch_duration(depth=1, extra_bytes_per_hour=0):
+def default_batch_duration(depth=1, extra_bytes_per_hour=0, extra_bytes=0):
     """Seconds of audio per streamed batch when the caller names none: four hours (measured best on a
     288 GB MI355X, see extract_features_streamed) unless `depth` such batches in flight would need more than
     half of the HBM that is free right now (_BATCH_BYTES_PER_HOUR each, plus `extra_bytes_per_hour`: a CREPE
-    pitch entry) - smaller devices get smaller batches instead of an out-of-memory error half way through a
-    corpus; never below ten minutes."""
+    pitch entry; `extra_bytes` per batch in flight whatever its duration: a bottleneck entry's bounded scratch) -
+    smaller devices get smaller batches instead of an out-of-memory error half way through a corpus; never below
+    ten minutes."""
     if _backend.device_count() < 1:   # (host-logic tests with the device pipeline replaced by a stand-in)
         return 14400.0
     free, _ = _backend.mem_info()
-    hours = (free // 2) / float((_BATCH_BYTES_PER_HOUR + extra_bytes_per_hour) * max(int(depth), 1))
+    depth = max(int(depth), 1)
+    hours = max(free // 2 - extra_bytes * depth, 0) / float((_BATCH_BYTES_PER_HOUR + extra_bytes_per_hour) * depth)
     return float(min(14400.0, max(600.0, 3600.0 * hours)))
 
 
@@ -1126,6 +1196,8 @@ class _Group:
     wait), or `abort` (an error: something may still be enqueued, plain free() waits for the device)."""
     def __init__(self, rate, idx):
         self.rate, self.idx = rate, idx
+        self.audio_rate = rate    # the rate of the 'wave' block: `rate`, or 8000 for a bottleneck entry (stage_audio)
+        self.from_resident = False   # the 'wave' block came from a _ResidentWaves, as an earlier pass left it
         self.blocks = {}
         self.soff = self.foff = self.pfoff = None
         self.dim = self.pdim = 0
@@ -1231,7 +1303,8 @@ class _PipelineRun:
         self.config, self.warps, self.log, self.tolerance = config, warps, log, tolerance
         self.resident, self.batch_id, self.stats = resident, batch_id, stats
         self.utterance_properties = utterance_properties
-        self.features_name = [k for k in config.keys() if k in valid_features()][0]
+        self.features_name = _features_of(config)
+        self.bottleneck = self.features_name == 'bottleneck'
         enabled = (lambda name: name in config) if stages is None else \
             (lambda name: name in config and name in stages)
         self.with_cmvn, self.with_delta, self.with_pitch = enabled('cmvn'), enabled('delta'), enabled('pitch')
@@ -1265,7 +1338,10 @@ class _PipelineRun:
         self.stage_audio()
         for group in self.groups:
             proc = _processor_class(self.features_name)(**self.config[self.features_name])
-            proc.sample_rate = group.rate
+            if not self.bottleneck:
+                proc.sample_rate = group.rate
+            elif group.rate != group.audio_rate:
+                proc.resample = 'kaldi'   # (what stage_audio did; the properties record it)
             if self.frame_length is None:
                 self.frame_length, self.frame_shift = proc.frame_length, proc.frame_shift
             if self.with_pitch and not stats_only:
@@ -1286,7 +1362,7 @@ class _PipelineRun:
                     # for uploads, the second for downloads - the GPU is idle in the first
                     self.resident.offer_track(
                         (self.batch_id, group.rate),
-                        _make_tracker(self.config, group.rate, self.frame_shift, self.frame_length, block.ptr,
+                        _make_tracker(self.config, group.audio_rate, self.frame_shift, self.frame_length, block.ptr,
                                       group.soff, self.stats, names=[self.names[i] for i in group.idx.tolist()]).job)
             else:
                 group.drop('wave')
@@ -1300,6 +1376,43 @@ class _PipelineRun:
 
     # ---- audio: one int16 block per sample rate in HBM ------------------------------------------------------
     def stage_audio(self):
+        self._upload_audio()
+        if self.bottleneck:
+            self._audio_to_8k()
+
+    def _audio_to_8k(self):
+        """A bottleneck entry: every group's audio becomes 8 kHz int16 before anything reads it, and the rest of
+        the pipeline sees that audio (reference pipeline_manager.py:228-245).  A group at another rate is
+        resampled on the device (Kaldi's ResampleWaveform on the int16 samples) and the 8 kHz block takes the
+        place of its 'wave' - also in the _ResidentWaves, so a later pass finds it made.  The groups stay per
+        source rate: their properties differ.  Utterances that are too short for one row are refused first, from
+        the lengths alone: nothing has been launched then."""
+        from shennong_amd.processor import bottleneck
+        proc = _processor_class('bottleneck')(**self.config['bottleneck'])
+        context = proc._network()[1].context
+        for group in self.groups:
+            resample = group.rate != 8000 and not group.from_resident
+            lengths = np.diff(group.soff)
+            if resample:
+                uniq, inverse = np.unique(lengths, return_inverse=True)
+                lengths = np.asarray([_backend.resample_num_out(group.rate, 8000, x) for x in uniq.tolist()],
+                                     dtype=np.int64)[inverse]
+            for k in np.flatnonzero(lengths < 200 + 80 * max(0, 2 * context - 10)).tolist():
+                message = bottleneck.too_short_message(int(lengths[k]), context, ' "{}"'.format(self.names[group.idx[k]]))
+                if message:
+                    raise ValueError(message)
+            if resample:
+                self.log.debug('resampling %d utterances from %d Hz to 8000 Hz', len(group.idx), group.rate)
+                t0 = time.perf_counter()
+                block, soff = _backend.resample_device(group.blocks['wave'], group.soff, group.rate, 8000, 0)
+                group.swap('wave', block)   # (the call returned: its stream is idle)
+                group.soff = soff
+                # (a plan-less entry point records no events: the host's clock around the call)
+                self._count(gpu_ms=1e3 * (time.perf_counter() - t0))
+            group.audio_rate = 8000
+        self.rate_of = [8000] * self.n
+
+    def _upload_audio(self):
         from shennong_amd.audio import Audio
         from shennong_amd.processor.base import check_signal
         utts, n, log = self.utts, self.n, self.log
@@ -1316,6 +1429,7 @@ class _PipelineRun:
             held = self.resident.take((self.batch_id, group.rate)) if self.resident is not None else None
             if held is not None:
                 block, group.soff = held
+                group.from_resident = True
                 group.hold('wave', block)
                 if self.view.prefetch is not None:
                     self.view.prefetch.cancel()
@@ -1352,6 +1466,7 @@ class _PipelineRun:
             held = self.resident.take((self.batch_id, rate)) if self.resident is not None else None
             if held is not None:
                 block, group.soff = held
+                group.from_resident = True
                 group.hold('wave', block)
                 continue
             mine = [utts[i] for i in idx.tolist()]
@@ -1374,12 +1489,14 @@ class _PipelineRun:
                     _backend.STAGING.release(token)
                 continue
             proc = _processor_class(self.features_name)(**self.config[self.features_name])
-            proc.sample_rate = rate
+            if not self.bottleneck:
+                proc.sample_rate = rate
             waves, checked = [], set()
             for utt in mine:
                 audio = utt.load_audio()
                 if (audio.nchannels, audio.sample_rate) not in checked:  # (one check per kind of signal)
-                    check_signal(proc, audio)
+                    if not self.bottleneck:   # (a bottleneck entry takes any rate; mono was checked above)
+                        check_signal(proc, audio)
                     checked.add((audio.nchannels, audio.sample_rate))
                 waves.append(audio.astype(np.int16).data)
             group.soff = _offsets([w.shape[0] for w in waves])
@@ -1405,8 +1522,8 @@ class _PipelineRun:
     # ---- pitch: needs nothing but the audio, runs on a side thread (its own streams) while this one takes the
     # audio through the features, VAD, CMVN and delta; waited for where the columns are joined ------------------
     def stage_pitch_start(self, group):
-        cache, rate = self.cache, group.rate
-        made = self.resident.take_track((self.batch_id, rate)) if self.resident is not None else None
+        cache, rate = self.cache, group.audio_rate
+        made = self.resident.take_track((self.batch_id, group.rate)) if self.resident is not None else None
         tracker = _make_tracker(self.config, rate, self.frame_shift, self.frame_length, group.ptr('wave'),
                                 group.soff, self.stats, start=made is None,
                                 names=[self.names[i] for i in group.idx.tolist()])
@@ -1429,6 +1546,8 @@ class _PipelineRun:
     # ---- the main features ------------------------------------------------------------------------------------
     def stage_features(self, group, proc):
         features_name, rate, cache, utts = self.features_name, group.rate, self.cache, self.utts
+        if self.bottleneck:
+            return self._stage_bottleneck(group, proc)
         plan = _backend.get_plan(proc._build_options())
         group.dim = dim = plan.ndims
         group.foff = foff = self._frame_offsets(plan, group.soff)
@@ -1460,16 +1579,57 @@ class _PipelineRun:
             self.classes.append(_Meta(cache[key], dim, t, cache[tkey], key))
         self.cls_of[group.idx] = base + inverse
 
+    def _stage_bottleneck(self, group, proc):
+        """The bottleneck entry's features: ONE extractor call on the group's 8 kHz block (too-short utterances
+        were refused in stage_audio), its rows written straight into the 'feat' block; the status words become
+        the processor's exceptions, in utterance order; one _Meta per row count"""
+        from shennong_amd.processor import bottleneck
+        cache, rate = self.cache, group.rate
+        device = _backend.get_device()
+        dnet = proc._device_network(device)
+        batch = bottleneck.BottleneckBatch.from_device(group.blocks['wave'], group.soff, device)
+        group.dim = dim = proc.ndims
+        group.foff = foff = _offsets(batch.rows(dnet.net.context))
+        group.hold('feat', _backend.DeviceBuffer(max(int(foff[-1]) * dim * 4, 16)))
+        self.log.debug('extract bottleneck on %d utterances at 8000 Hz (from %d Hz)', len(group.idx), rate)
+        t0 = time.perf_counter()
+        status = batch.extract(dnet, proc.dither, proc.precision, out=group.blocks['feat'], out_offsets=foff)[2]
+        # (a plan-less entry point records no events: the host's clock around the call, which returns when its
+        # stream is idle)
+        self._count(gpu_ms=1e3 * (time.perf_counter() - t0))
+        bottleneck.raise_for_status(status, [self.names[i] for i in group.idx.tolist()])
+        counts = np.diff(foff)
+        first, inverse = _classes_of(counts)
+        base = len(self.classes)
+        key = ('bottleneck', rate, None)
+        if key not in cache:
+            cache[key] = proc.get_properties()
+        for k in first.tolist():
+            t = int(counts[k])
+            tkey = ('times', 'bottleneck', rate, t)
+            if tkey not in cache:
+                cache[tkey] = proc.times(t)
+            self.classes.append(_Meta(cache[key], dim, t, cache[tkey], key))
+        self.cls_of[group.idx] = base + inverse
+
     # ---- energy -> VAD: the weights of the CMVN statistics --------------------------------------------------
     def stage_vad(self, group):
         DB = _backend.DeviceBuffer
         energy = _processor_class('energy')()
         energy.frame_length = self.frame_length
         energy.frame_shift = self.frame_shift
-        energy.sample_rate = group.rate
+        energy.sample_rate = group.audio_rate
         eplan = _backend.get_plan(energy._build_options())
         foff = group.foff
-        if not np.array_equal(self._frame_offsets(eplan, group.soff), foff):
+        efoff = self._frame_offsets(eplan, group.soff)
+        if self.bottleneck:
+            # (its row count is the energy's frame count at context 5 only: the reference's message, CMVN's
+            # accumulate, for the first utterance where they differ)
+            differ = np.flatnonzero(np.diff(efoff) != np.diff(foff))
+            if differ.size:
+                raise ValueError('there is {} weights but {} feature frames, must be equal'.format(
+                    int(np.diff(efoff)[differ[0]]), int(np.diff(foff)[differ[0]])))
+        if not np.array_equal(efoff, foff):
             raise ValueError('energy and features differ in number of frames')
         group.hold('energy', DB(max(int(foff[-1]) * 4, 16)))
         eplan.run_device(group.ptr('wave'), group.soff, foff, group.ptr('energy'), noise_call=_NOISE_CALL)
@@ -1667,7 +1827,7 @@ class _PipelineRun:
 def _extract_features_by_stage(config, utterances, warps, log, tolerance=2):
     """The same pipeline with every stage going through the host-pointer entry points of the
     processors (kept as the step-by-step cross-check of the device-resident path)"""
-    features_name = [k for k in config.keys() if k in valid_features()][0]
+    features_name = _features_of(config)
     with_cmvn = 'cmvn' in config
     if with_cmvn and config['cmvn']['by_speaker'] and not utterances.has_speakers():
         raise ValueError(
@@ -1706,15 +1866,31 @@ def _extract_features_by_stage(config, utterances, warps, log, tolerance=2):
     weights = [None] * n
     pitch = [None] * n
     frame_length = frame_shift = None
+    audio_rate_of = [m.sample_rate for m in meta_of]   # (the rate of the audio the processors see)
     for rate in samplerates:
         idx = [i for i in range(n) if meta_of[i].sample_rate == rate]
         group = [audios[i] for i in idx]
         proc = _processor_class(features_name)(**config[features_name])
-        proc.sample_rate = rate
+        if features_name == 'bottleneck':
+            # every signal becomes 8 kHz int16 first and the rest of the pipeline sees that audio (reference
+            # pipeline_manager.py:228-245), by the resampler of the device-resident path
+            group = [a.astype(np.int16) for a in group]
+            if rate != 8000:
+                group = [a.resample(8000, backend='kaldi') for a in group]
+                proc.resample = 'kaldi'   # (recorded in the properties; the audio is at 8 kHz already)
+            for i in idx:
+                audio_rate_of[i] = 8000
+            rate = 8000
+        else:
+            proc.sample_rate = rate
         if frame_length is None:
             frame_length, frame_shift = proc.frame_length, proc.frame_shift
         log.debug('extract %s on %d utterances at %d Hz', features_name, len(idx), rate)
-        if warps:
+        if features_name == 'bottleneck':
+            # (the batch's Features share one properties dictionary; each gets its own 'audio' / 'speaker' below)
+            out = [Features(f.data, f.times, dict(f.properties), validate=False)
+                   for f in proc._process_batch(group, names=[utts[i].name for i in idx])]
+        elif warps:
             out = proc._process_batch(group, vtln_warp=[warps[utts[i].name] for i in idx])
         else:
             out = proc._process_batch(group)
@@ -1757,7 +1933,7 @@ def _extract_features_by_stage(config, utterances, warps, log, tolerance=2):
         props['audio'] = {
             'file': (os.path.abspath(utt.audio_file)
                      if isinstance(utt.audio_file, str) else None),
-            'sample_rate': meta_of[i].sample_rate}
+            'sample_rate': audio_rate_of[i]}
         if utt.tstart is not None:
             props['audio']['tstart'] = utt.tstart
             props['audio']['tstop'] = utt.tstop

@@ -242,7 +242,8 @@ def _off(a):
 class BottleneckBatch:
     """The stages of one batch of 8 kHz int16 utterances on the device, each one batched launch through the C
     ABI: :meth:`vad`, :meth:`fbank`, :meth:`forward` (the tests and ``tools/time_bottleneck.py`` read the
-    intermediate buffers)"""
+    intermediate buffers); and all of them as one call that keeps no intermediate, :meth:`extract` (the
+    pipeline's entry)"""
 
     def __init__(self, waves, device=None):
         device = _backend.get_device() if device is None else int(device)
@@ -323,6 +324,75 @@ class BottleneckBatch:
 
     def host_bn(self):
         return self.bn.download(np.empty((int(self.roff[-1]), _NDIMS), dtype=np.float32))
+
+    def rows(self, context):
+        """Output rows of every utterance: frames + 10 - 2 `context`"""
+        return self.frames + 2 * _EDGE - 2 * int(context) - 20
+
+    def extract(self, dnet, dither=0.0, precision='float32', out=None, out_offsets=None, scratch_bytes=0,
+                seed=_DITHER_SEED):
+        """The whole extractor in ONE call (``snf_bottleneck_extract``): VAD, front end, context projection and the
+        two networks enqueued on one stream and waited for once, the intermediates in the calling thread's
+        bounded scratch (`scratch_bytes`, 0 = the library's default) - the bits of :meth:`vad`, :meth:`fbank`
+        and :meth:`forward` one after the other.  The rows of utterance u go to `out` (a DeviceBuffer of float32
+        rows of 80; None: a new one that holds them end to end) from row ``out_offsets[u]`` on (None: end to
+        end).  Returns ``(out, out_offsets, status)``: `status` [n] int32, bit 0 = no voiced frame, bit 1 = a
+        value that is not finite (:func:`raise_for_status`).  Nothing is downloaded."""
+        _check_precision(precision)
+        context = dnet.net.context
+        rows = self.rows(context)
+        if out_offsets is None:
+            out_offsets = np.zeros(self.n + 1, dtype=np.int64)
+            np.cumsum(rows, out=out_offsets[1:])
+        out_offsets = np.ascontiguousarray(out_offsets, dtype=np.int64)
+        if out_offsets.shape != (self.n + 1,):
+            raise ValueError(f'bottleneck: {self.n} utterances, {out_offsets.shape[0]} output offsets')
+        if out is None:
+            out = _backend.DeviceBuffer(max(16, 4 * _NDIMS * int(out_offsets[-1])), self.device)
+        elif self.n and 4 * _NDIMS * int(out_offsets[-1]) > out.nbytes:
+            raise ValueError('bottleneck: the output offsets reach past the output buffer')
+        if self.n and 2 * int(self.soff[-1]) > self.wave.nbytes:
+            raise ValueError('bottleneck: the sample offsets reach past the audio buffer')
+        basis = _device_array((self.device, context), lambda: _context_basis(context), self.device)
+        tables = _device_array(self.device, _front_tables, self.device)
+        status = np.zeros(self.n, dtype=np.int32)
+        bf16 = precision == 'bfloat16'
+        _backend.check(_backend.lib().snf_bottleneck_extract(
+            self.device, _p(self.wave), _off(self.soff), self.n, _p(tables), float(dither), int(seed), context,
+            _p(basis), dnet.widths, dnet.packed_pointers() if bf16 else dnet.pointers, int(bf16), _p(out),
+            _off(out_offsets), status.ctypes.data_as(C.POINTER(C.c_int32)), int(scratch_bytes), None))
+        return out, out_offsets, status
+
+    def runs(self, dnet, scratch_bytes=0):
+        """First utterance of every run :meth:`extract` walks under `scratch_bytes`, then the number of utterances"""
+        starts = np.zeros(self.n + 1, dtype=np.int64)
+        count = int(_backend.lib().snf_bottleneck_extract_runs(
+            _off(self.soff), self.n, dnet.net.context, dnet.widths, int(scratch_bytes), _off(starts)))
+        if count < 0:
+            _backend.check(count)
+        return starts[:count + 1] if self.n else starts[:0]
+
+
+def too_short_message(length, context, label=''):
+    """The ValueError text for a signal of `length` samples at 8 kHz that gives no row of features; None when
+    it gives some"""
+    rows = num_frames(length) + 2 * _EDGE - 2 * context - 20
+    if num_frames(length) >= 1 and rows >= 1:
+        return None
+    return 'signal{} too short: {} samples at 8 kHz give {} frames, one row of features needs {}'.format(
+        label, length, num_frames(length), max(1, 2 * context + 21 - 2 * _EDGE))
+
+
+def raise_for_status(status, names=None):
+    """The processor's exceptions for the status words of :meth:`BottleneckBatch.extract`, the first utterance
+    in order that has one: RuntimeError for an utterance without voiced frames, ValueError (the text of
+    ``_backend._check_finite``) for values that are not finite"""
+    for i in np.flatnonzero(status).tolist():
+        if status[i] & 1:
+            label = '' if names is None else ' "{}"'.format(names[i])
+            raise RuntimeError('no voice detected in signal{}, failed to extract features'.format(label))
+        if status[i] & 2:
+            raise ValueError('data contains non-finite numbers (nan of infinity)')
 
 
 def dense_layer(x, w, b, act='identity', device=None, precision='float32'):
@@ -564,11 +634,9 @@ class BottleneckProcessor(FeaturesProcessor):
             return '' if names is None else ' "{}"'.format(names[i])
 
         for i, length in enumerate(lengths):
-            rows = num_frames(length) + 2 * _EDGE - 2 * context - 20
-            if num_frames(length) < 1 or rows < 1:
-                raise ValueError(
-                    'signal{} too short: {} samples at 8 kHz give {} frames, one row of features needs {}'.format(
-                        label(i), length, num_frames(length), max(1, 2 * context + 21 - 2 * _EDGE)))
+            message = too_short_message(int(length), context, label(i))
+            if message:
+                raise ValueError(message)
         if self._resample == 'kaldi':
             batch = BottleneckBatch.from_device(*_backend.upload_resampled(waves, rates, 8000, lengths, device))
         else:
