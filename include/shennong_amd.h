@@ -671,6 +671,38 @@ int snf_linear_resample(int device_id, int32_t rate_in, int32_t rate_out, int32_
                         const int64_t* h_src_offsets, int64_t n_utts, void* d_dst, const int64_t* h_dst_starts,
                         void* stream);
 
+/* ---- padded batches from a ragged block (Kaldi splice-feats + subsample-feats, then padding) ----
+ * An extension with no reference call behind it: the reference returns one numpy array per utterance and leaves
+ * batching to its caller.  For a consumer on the same GPU, the float32 block [rows, dim] that a run call left in
+ * HBM becomes the tensor [n_utts, t_max, dim (left + 1 + right)] that a model reads, in one pass.
+ */
+#define SNF_COLLATE_F32 0  /* a copy                                                         */
+#define SNF_COLLATE_F16 1  /* IEEE binary16, to nearest (ties to even), overflow to infinity */
+#define SNF_COLLATE_BF16 2 /* bfloat16, to nearest (ties to even); a NaN stays a NaN         */
+/* Frames that subsample-feats keeps of `frames`: offset, offset + subsample, ...: 0 when frames <= offset, else
+ * (frames - offset + subsample - 1) / subsample.  Host only.  < 0: SNF_E_INVALID (frames < 0, subsample < 1, or
+ * offset outside [0, subsample)). */
+int64_t snf_collate_num_out(int64_t frames, int32_t subsample, int32_t offset);
+/* With T_u = h_frame_offsets[u + 1] - h_frame_offsets[u], n_u = snf_collate_num_out(T_u, subsample, offset),
+ * j < t_max and k in [-left, right]:
+ *   d_out[u][j][(k + left) dim + d] = cast(d_in[h_frame_offsets[u] + clamp(offset + j subsample + k, 0, T_u - 1)][d])
+ *                                                                                                   if j <  n_u
+ *   d_out[u][j][:]                  = cast(pad_value)                                               if j >= n_u
+ *   d_lengths[u]                    = n_u   (int32)
+ * The edge rule is the one of Kaldi's splice-feats (the first and last frame are repeated), the frame selection
+ * the one of subsample-feats.  `out_type`: SNF_COLLATE_*.  d_in is float32 [h_frame_offsets[n_utts], dim]; d_out
+ * holds n_utts * t_max * dim * (left + 1 + right) elements and is 16-byte aligned; every byte of d_out and of
+ * d_lengths is written.  SNF_E_INVALID, before any device work: t_max < max n_u, subsample < 1, offset outside
+ * [0, subsample), a negative context, dim < 1, an unknown out_type, offsets that decrease or start below 0, a
+ * misaligned d_out, or an output of 2^31 elements or more (the kernel indexes it with 32 bits).  The offsets
+ * table is a HOST array that the call uploads.  Everything is enqueued on `stream` and the call returns without
+ * waiting for it (the table is kept in a slot of its own until the kernel has read it); `stream` NULL: the
+ * calling thread's own stream, which the call waits for before returning. */
+int snf_collate_padded(int device_id, const float* d_in, int32_t dim, const int64_t* h_frame_offsets,
+                       int64_t n_utts, int32_t left, int32_t right, int32_t subsample, int32_t offset,
+                       int32_t out_type, float pad_value, int64_t t_max, void* d_out, int32_t* d_lengths,
+                       void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

@@ -48,7 +48,8 @@ EXPORTS = [
     'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot', 'snf_packed_weights_bf16_size',
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
     'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
-    'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs']
+    'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs',
+    'snf_collate_num_out', 'snf_collate_padded']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -199,6 +200,9 @@ def lib():
         L.snf_resample_num_out.argtypes = [i32, i32, i64]
         L.snf_resample_num_out.restype = i64
         L.snf_linear_resample.argtypes = [i32, i32, i32, i32, vp, pi64, i64, vp, pi64, vp]
+        L.snf_collate_num_out.argtypes = [i64, i32, i32]
+        L.snf_collate_num_out.restype = i64
+        L.snf_collate_padded.argtypes = [i32, vp, i32, pi64, i64, i32, i32, i32, i32, i32, f32, i64, vp, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)
@@ -463,9 +467,27 @@ class Plan:
         ONE validation of the whole batch (what Features.validate checks per utterance).  With `wrap` the
         call returns ``wrap(matrices)`` instead - the caller's per-utterance objects, which a large batch
         builds while its pieces are still on their way (they only need to know WHERE their rows will be)"""
-        if wrap is not None:
-            return self._run(waves, vtln_warps, check_finite, wrap)
-        return self._run(waves, vtln_warps, check_finite, lambda res: res)
+        wrap = wrap or (lambda res: res)
+        if getattr(_RESIDENT, 'sink', None) is not None:
+            return self._run_to_sink(waves, vtln_warps, check_finite, None, wrap)
+        return self._run(waves, vtln_warps, check_finite, wrap)
+
+    def _run_to_sink(self, waves, vtln_warps, check_finite, pinned, wrap):
+        """`run` / `run_pinned` inside :class:`resident_results`: the block stays in HBM and goes to the sink;
+        the caller's `wrap` gets placeholders of the matrices' shapes, from which it builds the same times and
+        properties as ever"""
+        block, foff, wrapped = self.run_resident(waves, vtln_warps, check_finite, pinned=pinned, wrap=wrap)
+        _RESIDENT.sink.append((block, foff, self.ndims))
+        return wrapped
+
+    @staticmethod
+    def _placeholders(nfr, ndims):
+        """One read-only array per utterance with the shape of its matrix and no memory behind it (one zero,
+        broadcast; one object per distinct frame count).  Kaldi returns an empty (0, 0) matrix when no frame fits."""
+        zero = np.float32(0)
+        made = {rows: np.broadcast_to(zero, (rows, ndims)) if rows else np.zeros((0, 0), dtype=np.float32)
+                for rows in np.unique(nfr).tolist()}
+        return [made[rows] for rows in nfr.tolist()]
 
     def _run(self, waves, vtln_warps, check_finite, wrap):
         n = len(waves)
@@ -581,6 +603,8 @@ class Plan:
             if np.all(warp == 1.0):
                 warp = None
         wrap = wrap or (lambda res: res)
+        if getattr(_RESIDENT, 'sink', None) is not None:
+            return self._run_to_sink(None, vtln_warps, check_finite, corpus, wrap)
         if n == 0:
             return wrap([])
         cuts = self._tracker_chunks(soff)
@@ -593,7 +617,7 @@ class Plan:
             return self._run(corpus.views, vtln_warps, check_finite, wrap)
         return self._run_large(corpus.views, soff, foff, nfr, warp, check_finite, wrap, pinned=corpus)
 
-    def _run_large(self, waves, soff, foff, nfr, warp, check_finite, wrap, pinned=None):
+    def _run_large(self, waves, soff, foff, nfr, warp, check_finite, wrap, pinned=None, resident=False):
         """`run` for batches of tens of megabytes and more (process_all over a corpus).  The batch is cut into
         pieces of whole utterances (~16); each copy thread takes every fourth piece through the whole path on
         its own stream and its own clone of the plan: gather into page-locked memory -> upload -> kernel ->
@@ -601,7 +625,9 @@ class Plan:
         of another and the download of a third overlap (the link is full duplex) and the call costs little more
         than its upload.  The batch is validated while it is in HBM (one count over the whole output instead of
         two passes over the host copy); the per-utterance views are cut while the pieces are in flight.
-        10 000 x 3 s utterances, fbank-40: upload, kernel, download one after the other took 36 ms (round 4)."""
+        10 000 x 3 s utterances, fbank-40: upload, kernel, download one after the other took 36 ms (round 4).
+        `resident` (:func:`run_resident`): no download and no host views - `wrap` gets placeholders, and the
+        validated device block is returned beside what it made."""
         global _COPY_POOL
         n = len(waves)
         total = int(foff[-1])
@@ -615,7 +641,7 @@ class Plan:
         try:
             d_wave = DeviceBuffer(max(total_samples * 2, 16), self.device)
             d_out = DeviceBuffer(max(total * ndims * 4, 16), self.device)
-            out = result_array((total, ndims), np.float32)
+            out = None if resident else result_array((total, ndims), np.float32)
             pieces = max(1, min(_COPY_PIECES * _COPY_THREADS, n, total_samples * 2 // (8 << 20)))
             if self.opts.kind == _abi.KIND_PITCH:
                 # (the tracker's cost per utterance falls with the size of a call - 250 / 1 000 / 10 000 utterances:
@@ -648,7 +674,7 @@ class Plan:
                 with _LOCK:
                     if _COPY_POOL is None:
                         _COPY_POOL = ThreadPoolExecutor(max_workers=_COPY_THREADS, thread_name_prefix='snf-copy')
-            base_in, base_out = staged.ctypes.data, out.ctypes.data
+            base_in, base_out = staged.ctypes.data, None if resident else out.ctypes.data
             L = lib()
             up, down = _shared_stream(self.device, 0), _shared_stream(self.device, 1)
             noise_call = self._next_noise_call()   # (ONE number for the call: every piece draws from its stream)
@@ -676,6 +702,8 @@ class Plan:
                                              d_out.ptr + 4 * ndims * f0,
                                              vtln_warps=None if warp is None else warp[a:b], stream=down,
                                              noise_call=noise_call)
+                        if resident:
+                            return
                         check(L.snf_memcpy_d2h_async(C.c_void_p(base_out + 4 * ndims * f0),
                                                      C.c_void_p(d_out.ptr + 4 * ndims * f0),
                                                      4 * ndims * (f1 - f0), C.c_void_p(down)))
@@ -702,14 +730,14 @@ class Plan:
                         if cuts[k + 1] > cuts[k]:
                             enqueue(k)
                 res = []
-                for u in range(n):   # (cut while the pieces are in flight)
+                for u in range(0 if resident else n):   # (cut while the pieces are in flight)
                     if nfr[u] == 0:
                         res.append(np.zeros((0, 0), dtype=np.float32))   # Kaldi: an empty (0, 0) matrix
                     elif n == 1:
                         res.append(out)
                     else:
                         res.append(out[foff[u]:foff[u + 1]])
-                res = wrap(res)
+                res = wrap(self._placeholders(nfr, ndims) if resident else res)
             finally:
                 # whatever happened: no thread is still enqueuing, nothing is in flight on these buffers afterwards
                 wait(futures)
@@ -731,8 +759,75 @@ class Plan:
             del staged
             STAGING.release(token)
         d_wave.free(synced=True)   # every copy thread synchronised its stream
+        if resident:
+            return d_out, res
         d_out.free(synced=True)
         return res
+
+    def run_resident(self, waves, vtln_warps=None, check_finite=False, pinned=None, wrap=None):
+        """`run` (or `run_pinned` with `pinned`, a page-locked corpus) whose result STAYS in HBM: ->
+        ``(DeviceBuffer float32 [frames, ndims], frame offsets [utterances + 1], wrap(placeholders))``, complete
+        and - with `check_finite` - validated on the device when the call returns; the caller owns the block.
+        `wrap` builds the caller's per-utterance objects from arrays that have the matrices' shapes and no
+        memory (`_placeholders`), while a large batch is still in flight, as in `run`.  Same
+        launches as the host call: a small batch goes up whole and through `run_device` on the plan's stream
+        (what snf_plan_run_batch does between its two copies), a large one through `_run_large` without its
+        downloads.  A pitch batch beyond `_MAX_TRACKER_HOURS`, which the host call runs as several calls one
+        after the other, is refused: its scratch and its result would not share the HBM."""
+        if pinned is not None:
+            waves, soff = pinned.views, pinned.soff
+            n = soff.shape[0] - 1
+        else:
+            n = len(waves)
+            i16 = np.dtype(np.int16)
+            if any(w.dtype != i16 or w.ndim != 1 for w in waves):
+                waves = [np.ascontiguousarray(w, dtype=np.int16).reshape(-1) for w in waves]
+            soff = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum(np.fromiter((w.shape[0] for w in waves), np.int64, n), out=soff[1:])
+        lengths = np.diff(soff)
+        frames_of = {int(x): self.num_frames(int(x)) for x in np.unique(lengths)}
+        nfr = np.fromiter((frames_of[int(x)] for x in lengths), np.int64, n)
+        foff = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(nfr, out=foff[1:])
+        warp = None
+        if vtln_warps is not None:
+            warp = np.ascontiguousarray(vtln_warps, dtype=np.float32)
+            if warp.shape[0] != n:
+                raise ValueError('one vtln_warp per utterance is required')
+            if np.all(warp == 1.0):
+                warp = None
+        wrap = wrap or (lambda res: res)
+        ndims = self.ndims
+        if ndims <= 0:
+            raise ValueError('this plan has no output columns')
+        if self._tracker_chunks(soff) is not None:
+            raise ValueError(f'more than {_MAX_TRACKER_HOURS:g} hours of audio in one device-resident pitch call: '
+                             'use process_all, or call per part of the corpus')
+        total, total_samples = int(foff[-1]), int(soff[-1])
+        if n and total_samples * 2 >= _LARGE_BATCH_BYTES:
+            d_out, wrapped = self._run_large(waves, soff, foff, nfr, warp, check_finite, wrap, pinned=pinned,
+                                             resident=True)
+            return d_out, foff, wrapped
+        d_out = DeviceBuffer(max(total * ndims * 4, 16), self.device)
+        if total == 0:
+            return d_out, foff, wrap(self._placeholders(nfr, ndims))
+        d_wave = None
+        try:
+            if pinned is not None:
+                d_wave = DeviceBuffer(max(total_samples * 2, 16), self.device)
+                d_wave.upload(pinned.block[:total_samples])
+            else:
+                d_wave = upload_rows(waves, np.int16, self.device)
+            self.run_device(d_wave.ptr, soff, foff, d_out.ptr, vtln_warps=warp)   # (waits for the plan's stream)
+            if check_finite:
+                check_finite_device(d_out.ptr, total * ndims, self.device)
+        except BaseException:
+            for block in (d_wave, d_out):
+                if block is not None:
+                    block.free()
+            raise
+        d_wave.free(synced=True)
+        return d_out, foff, wrap(self._placeholders(nfr, ndims))
 
     # -- Features -> Features --
     def run_post(self, mats, check_finite=False):
@@ -885,6 +980,57 @@ def concat_columns_device(d_a, cols_a, off_a, d_b, cols_b, off_b, d_out, off_out
         _DEVICE if device is None else int(device), C.c_void_p(d_a), cols_a,
         off_a.ctypes.data_as(p64), C.c_void_p(d_b), cols_b, off_b.ctypes.data_as(p64), n,
         C.c_void_p(d_out), off_out.ctypes.data_as(p64)))
+
+
+_RESIDENT = threading.local()
+
+
+class resident_results:
+    """Inside this context the plan calls of THIS thread (`Plan.run`, `Plan.run_pinned`) leave their results in
+    HBM: `blocks` collects one ``(DeviceBuffer, frame offsets, ndims)`` per call and the matrices handed to the
+    caller's `wrap` are placeholders of the right shapes.  Everything before and after the plan call - the
+    processors' checks, their input routes, their times and properties - is the code of the host call
+    (``FeaturesProcessor.process_all_device``).  The blocks belong to whoever leaves the context without an
+    exception; with one they are given back."""
+    def __enter__(self):
+        self.blocks = []
+        self._outer = getattr(_RESIDENT, 'sink', None)
+        _RESIDENT.sink = self.blocks
+        return self
+
+    def __exit__(self, kind, value, trace):
+        _RESIDENT.sink = self._outer
+        if kind is not None:
+            for block, _, _ in self.blocks:
+                block.free()
+            self.blocks = []
+        return False
+
+
+COLLATE_TYPES = {'float32': 0, 'float16': 1, 'bfloat16': 2}   # snf_collate_padded's out_type
+
+
+def collate_num_out(frames, subsample=1, offset=0):
+    """Frames that subsampling keeps of `frames`: offset, offset + subsample, ... (snf_collate_num_out)"""
+    n = int(lib().snf_collate_num_out(int(frames), int(subsample), int(offset)))
+    if n < 0:
+        check(n)
+    return n
+
+
+def collate_padded(d_in, dim, foff, dtype, left, right, subsample, offset, pad_value, t_max, d_out, d_lengths,
+                   device=None, stream=None):
+    """Ragged float32 rows at the device pointer `d_in` ([foff[-1], dim], utterance boundaries `foff`) -> the
+    padded batch [utterances, t_max, dim (left + 1 + right)] of `dtype` at `d_out` and the kept frame counts
+    (int32) at `d_lengths`: see snf_collate_padded in include/shennong_amd.h"""
+    foff = np.ascontiguousarray(foff, dtype=np.int64)
+    if dtype not in COLLATE_TYPES:
+        raise ValueError('invalid dtype "{}", choose in "{}"'.format(dtype, ', '.join(COLLATE_TYPES)))
+    check(lib().snf_collate_padded(
+        _DEVICE if device is None else int(device), C.c_void_p(d_in), int(dim),
+        foff.ctypes.data_as(C.POINTER(C.c_int64)), foff.shape[0] - 1, int(left), int(right), int(subsample),
+        int(offset), COLLATE_TYPES[dtype], float(pad_value), int(t_max), C.c_void_p(d_out), C.c_void_p(d_lengths),
+        C.c_void_p(stream) if stream else None))
 
 
 def check_finite_device(d_ptr, count, device=None):

@@ -350,6 +350,18 @@ int launch_concat_columns(const float* a, int cols_a, const int64_t* d_off_a, co
                           const int64_t* d_off_b, int64_t n_utts, float* out, const int64_t* d_off_out,
                           int64_t total_rows, hipStream_t stream);
 int launch_count_nonfinite(const float* x, uint64_t n, unsigned long long* d_count, hipStream_t stream);
+// kernels_collate.hip: ragged block -> padded batch (snf_collate_padded)
+struct CollateUtt {
+  int64_t row0;     // first row of the utterance in the block
+  int32_t frames;   // its rows
+  int32_t n_out;    // the rows kept of it (snf_collate_num_out)
+};
+struct CollateShape {
+  int32_t dim, width, left, subsample, offset, t_max;   // width = left + 1 + right
+  uint32_t row_elems, utt_elems, total, n_utts;         // dim width, t_max row_elems, n_utts utt_elems
+};
+int launch_collate_padded(const float* in, const CollateUtt* d_utts, const CollateShape& shape, int out_type,
+                          float pad_value, void* out, int32_t* lengths, hipStream_t stream);
 int launch_sliding_cmvn(const snf_sliding_cmvn_options& o, const float* in, int in_cols,
                         const int64_t* frame_offsets, int64_t n_utts, float* out,
                         hipStream_t stream);

@@ -442,6 +442,42 @@ def extract_features(configuration, utterances, warps=None, njobs=1,
     return _extract_features(config, _view_of(utterances), warps, log)
 
 
+def extract_features_device(configuration, utterances, warps=None, njobs=1,
+                            log=get_logger('pipeline', 'warning')):
+    """:func:`extract_features` whose result stays on the GPU (an extension: the reference has no such call)
+
+    Same arguments, checks and stages, but the final matrices are not downloaded: returns a
+    :class:`~shennong_amd.device.DeviceFeaturesCollection` (one device block per sample rate of the corpus) whose
+    ``to_host()`` is what :func:`extract_features` returns, bit for bit.  Every pipeline configuration is served,
+    CREPE pitch and bottleneck features included.
+
+    Raises a ValueError, beside those of :func:`extract_features`, for a corpus that does not fit one device
+    batch: :func:`extract_features_streamed` takes a corpus of any size in bounded batches, to the host.
+    """
+    from shennong_amd.device import DeviceFeaturesCollection
+    get_njobs(njobs, log=log)
+    config = _init_config(configuration, log=log)
+    log.info('detected format for utterances index is: %s',
+             utterances.format(type=str))
+    warps, config = _train_vtln(config, utterances, warps, njobs, log)
+    if _sized(_too_large_for_one_batch, utterances, config):
+        raise ValueError(
+            'the corpus does not fit one device batch, and a device-resident result is one batch: use '
+            'extract_features_streamed (bounded batches, results on the host) or call per part of the corpus')
+    if warps:
+        warps = _init_warps(warps, config, utterances, log)
+    blocks = []
+    try:
+        # (the `device_out` route of the sharded driver: the Features carry shapes, times and properties over
+        # host arrays that are never written)
+        template = _extract_features(config, _view_of(utterances), warps, log, device_out=blocks)
+    except BaseException:
+        for block, _, _ in blocks:
+            block.free()
+        raise
+    return DeviceFeaturesCollection._build(template, blocks)
+
+
 def _too_large_for_one_batch(utterances, extra_bytes_per_hour=0, extra_bytes=0):
     """True when one batch over all of `utterances` would need more than half of the HBM that is free
     (_BATCH_BYTES_PER_HOUR per hour of audio while a batch is in flight, plus `extra_bytes_per_hour`: a CREPE

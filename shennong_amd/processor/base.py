@@ -102,6 +102,30 @@ class FeaturesProcessor(BaseProcessor, metaclass=abc.ABCMeta):
         with paused_gc():
             return self._process_all(utterances, **kwargs)
 
+    def process_all_device(self, utterances, njobs=None, **kwargs):
+        """`process_all` whose result stays on the GPU (an extension: the reference has no such call)
+
+        Same arguments, input routes (pinned corpus, WAV files, in-memory audio), checks and finite-data
+        validation as :func:`process_all`, but no download: returns a
+        :class:`~shennong_amd.device.DeviceFeaturesCollection` whose ``to_host()`` is what `process_all` returns,
+        bit for bit.  For the processors that run through one batched plan call: spectrogram, filterbank, MFCC,
+        PLP, energy and Kaldi pitch.  The others raise NotImplementedError: bottleneck and CREPE features stay
+        on the device through :func:`shennong_amd.pipeline.extract_features_device`.
+        """
+        from shennong_amd.device import DeviceFeaturesCollection
+        if not hasattr(self, '_process_pinned'):
+            raise NotImplementedError(
+                f'{type(self).__name__} has no device-resident process_all: use '
+                'shennong_amd.pipeline.extract_features_device, which keeps the features of a pipeline '
+                'configuration (bottleneck and CREPE pitch included) on the device')
+        njobs = get_njobs(njobs, log=self.log)
+        with paused_gc():
+            with _backend.resident_results() as resident:
+                template = self._process_all(utterances, **kwargs)
+            # (every processor served here makes ONE plan call per batch: one block, rows in utterance order)
+            return DeviceFeaturesCollection._build(
+                template, [(block, list(template), ndims) for block, _, ndims in resident.blocks])
+
     def _process_all(self, utterances, **kwargs):
         for name, value in kwargs.items():
             if not isinstance(value, dict):
