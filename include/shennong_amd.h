@@ -703,6 +703,34 @@ int snf_collate_padded(int device_id, const float* d_in, int32_t dim, const int6
                        int32_t out_type, float pad_value, int64_t t_max, void* d_out, int32_t* d_lengths,
                        void* stream);
 
+/* ---- DTW distances between feature items (the step after extraction in the reference's worked examples) ----
+ * An extension with no reference call behind it: both examples of the reference extract features and then run
+ * `abx-distance -n 1` of an external toolkit on the CPU (reference examples/features_abx/scripts/abx_score.sh:21),
+ * one pair at a time.  Here the pairs of one call are computed on the device from rows that lie in HBM.  The
+ * definition is this project's own (tests/dtw_f64.py); agreement with that toolkit is unpinned.
+ */
+#define SNF_DTW_COSINE 0       /* acos(clamp(cos(x_i, y_j), -1, 1)) / pi; 1 if one row is zero, 0 if both */
+#define SNF_DTW_SQEUCLIDEAN 1  /* sum_k (x_ik - y_jk)^2, as max(|x_i|^2 + |y_j|^2 - 2 x_i . y_j, 0)      */
+#define SNF_DTW_MAX_FRAMES 4096 /* rows of one item */
+#define SNF_DTW_MAX_DIM 4096
+/* Item t is the rows [h_item_first[t], h_item_first[t] + h_item_count[t]) of the float32 block d_rows [., dim];
+ * pair p = (h_pairs[2 p], h_pairs[2 p + 1]) = (x, y) indexes the items.  With d[i][j] the frame distance of row i
+ * of x and row j of y (`metric`: SNF_DTW_*):
+ *   C[0][0] = d[0][0], L[0][0] = 1;  C[i][j] = d[i][j] + C[q], L[i][j] = L[q] + 1, q the predecessor of smallest
+ *   C among (i-1, j-1), (i-1, j), (i, j-1) where they exist, ties to the first of that order;
+ *   d_cost[p] = C[N-1][M-1] (float32 sums), d_len[p] = L[N-1][M-1]: the normalised distance is their quotient.
+ * Results are in the caller's pair order and every element of d_cost and d_len is written; a pair's result does
+ * not depend on the other pairs of the call.  Non-finite features give undefined values, nothing worse.
+ * SNF_E_INVALID, before any device work: dim outside [1, SNF_DTW_MAX_DIM], n_items < 1, n_pairs < 0, an item
+ * that starts below row 0 or has fewer than 1 or more than SNF_DTW_MAX_FRAMES rows, a pair index outside
+ * [0, n_items), an unknown metric, a null or misaligned pointer.  n_pairs = 0 does nothing.  The tables are HOST
+ * arrays that the call uploads.  Everything is enqueued on `stream` and the call returns without waiting for it
+ * (the tables and the row norms are kept in a slot of their own until the kernels have run); `stream` NULL: the
+ * calling thread's own stream, which the call waits for before returning. */
+int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                  const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
+                  int32_t metric, float* d_cost, int32_t* d_len, void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

@@ -49,7 +49,7 @@ EXPORTS = [
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
     'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
     'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs',
-    'snf_collate_num_out', 'snf_collate_padded']
+    'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -203,6 +203,7 @@ def lib():
         L.snf_collate_num_out.argtypes = [i64, i32, i32]
         L.snf_collate_num_out.restype = i64
         L.snf_collate_padded.argtypes = [i32, vp, i32, pi64, i64, i32, i32, i32, i32, i32, f32, i64, vp, vp, vp]
+        L.snf_dtw_pairs.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, vp, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)
@@ -1031,6 +1032,26 @@ def collate_padded(d_in, dim, foff, dtype, left, right, subsample, offset, pad_v
         foff.ctypes.data_as(C.POINTER(C.c_int64)), foff.shape[0] - 1, int(left), int(right), int(subsample),
         int(offset), COLLATE_TYPES[dtype], float(pad_value), int(t_max), C.c_void_p(d_out), C.c_void_p(d_lengths),
         C.c_void_p(stream) if stream else None))
+
+
+DTW_METRICS = {'cosine': 0, 'sqeuclidean': 1}   # snf_dtw_pairs' metric
+DTW_MAX_FRAMES = 4096                            # SNF_DTW_MAX_FRAMES
+
+
+def dtw_pairs(d_rows, dim, item_first, item_count, pairs, metric, d_cost, d_len, device=None, stream=None):
+    """DTW cost (float32 at `d_cost`) and path length (int32 at `d_len`) of every pair of `pairs` [P, 2], which
+    indexes the items `item_first`, `item_count` (rows of the float32 block [., dim] at the device pointer
+    `d_rows`): see snf_dtw_pairs in include/shennong_amd.h"""
+    first = np.ascontiguousarray(item_first, dtype=np.int64)
+    count = np.ascontiguousarray(item_count, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if metric not in DTW_METRICS:
+        raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(DTW_METRICS)))
+    check(lib().snf_dtw_pairs(
+        _DEVICE if device is None else int(device), C.c_void_p(d_rows), int(dim),
+        first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int32)), first.shape[0],
+        pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], DTW_METRICS[metric], C.c_void_p(d_cost),
+        C.c_void_p(d_len), C.c_void_p(stream) if stream else None))
 
 
 def check_finite_device(d_ptr, count, device=None):

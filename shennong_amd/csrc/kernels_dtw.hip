@@ -1,0 +1,263 @@
+// Dynamic time warping between pairs of feature items (snf_dtw_pairs; an extension: the reference's users leave
+// the GPU for this step, examples/features_abx/scripts/abx_score.sh:21).  For the items x [N, D] and y [M, D]:
+//
+//   d[i][j]  cosine:      acos(clamp(x_i . y_j / (|x_i| |y_j|), -1, 1)) / pi; 1 if one of the rows is zero, 0 if both
+//            sqeuclidean: max(|x_i|^2 + |y_j|^2 - 2 x_i . y_j, 0)
+//   C[0][0] = d[0][0], L[0][0] = 1;   C[i][j] = d[i][j] + C[p], L[i][j] = L[p] + 1
+//   p = the predecessor of smallest C among (i-1, j-1), (i-1, j), (i, j-1), ties to the first of that order
+//   cost = C[N-1][M-1], len = L[N-1][M-1]
+//
+// Pre-pass (dtw_rows_kernel): one thread per row of the block writes 1 / |row| (0 for a zero row) or |row|^2, the
+// sum of squares being one fused chain over k ascending.
+//
+// Main kernel (dtw_pairs_kernel): one wavefront (a workgroup of 64) owns a pair and walks the pairs of its class
+// with the stride of the grid; the host has sorted every class by N M descending, so the strided walk hands
+// every wave a like share.  Nothing in it loops on data: every bound is a frame count the host has checked.
+//   * x is cut into strips of 64 rows, lane = row of the strip.  The columns come in tiles of 32: the 64 x 32
+//     dot products of a tile are two v_mfma_f32_32x32x2_f32 chains over k (lane l supplies x[l & 31][k0 + (l >> 5)]
+//     and y[l & 31][k0 + (l >> 5)] straight from memory, zeros beyond an odd D; rows and columns beyond the item
+//     repeat its last one and are never read back).  The chain is bit for bit fmaf over k ascending from zero.
+//   * The epilogue turns the accumulators (row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31) into distances
+//     and writes them to a ring of SLOTS tiles in LDS, row stride S = 32 SLOTS floats: a half-wave writes 32
+//     consecutive words of one row.  The norms of the strip's rows sit in LDS (a broadcast read), the column's
+//     norm in a register.
+//   * The dynamic programme is skewed: at step t lane i does cell (i, t - i), so the tile T is made at step 32 T,
+//     when lane 0 first needs it, and the lanes behind still read the tiles T - 1 and T - 2: SLOTS = 3 (one when
+//     the pair has at most 32 columns).  The read of lane i is word i S + (t - i) mod S: bank (t - i) mod 32, a
+//     bijection over each half-wave.
+//   * Lane i gets (C, L) of cell (i - 1, t - i), which lane i - 1 made at step t - 1, through a DPP rotation; what it
+//     got one step earlier is its diagonal neighbour; its own last cell is the left one.  C is float32, L int32.
+//   * Strip seams: lane 63 leaves (C, L) per column in a seam row in LDS (8 bytes per column); lane 0 of the next
+//     strip reads column t at step t, 63 steps before lane 63 overwrites it - in place.
+// Three instances by the columns of a pair (LDS per wave): M <= 32 (8.5 KB), M <= 512 (28.3 KB), M <= 4096 (56.3 KB).
+#include <math.h>
+
+#include "snf_internal.h"
+
+namespace snf {
+
+int dtw_class_of(int32_t columns) { return columns <= 32 ? 0 : columns <= 512 ? 1 : 2; }
+
+namespace {
+
+constexpr int kSeam[kDtwClasses] = {32, 512, kDtwMaxFrames};
+constexpr int kWavesPerCu[kDtwClasses] = {16, 5, 2};   // what the LDS of a compute unit (160 KB) holds
+
+__global__ __launch_bounds__(256) void dtw_rows_kernel(const float* __restrict__ rows, const int dim,
+                                                       const int64_t row_lo, const int64_t n, const int metric,
+                                                       float* __restrict__ aux) {
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (r >= n) return;
+  const float* p = rows + (row_lo + r) * dim;
+  float s = 0.0f;
+  for (int k = 0; k < dim; ++k) s = fmaf(p[k], p[k], s);
+  aux[r] = metric == SNF_DTW_COSINE ? (s > 0.0f ? 1.0f / sqrtf(s) : 0.0f) : s;
+}
+
+template <int METRIC>
+__device__ __forceinline__ float frame_distance(float dot, float xa, float ya) {
+  if constexpr (METRIC == SNF_DTW_COSINE) {
+    float c = dot * xa * ya;
+    c = fminf(fmaxf(c, -1.0f), 1.0f);
+    const float d = acosf(c) * 0.31830988618379067f;
+    const bool xz = xa == 0.0f, yz = ya == 0.0f;
+    return (xz || yz) ? ((xz && yz) ? 0.0f : 1.0f) : d;
+  } else {
+    return fmaxf(fmaf(-2.0f, dot, xa + ya), 0.0f);
+  }
+}
+
+// (C, L) of lane - 1: a DPP move with wave_ror:1 (gfx9 keeps the whole-wave rotations: device_fft1024.h), not a
+// trip through the LDS crossbar (ds_bpermute measured within 1 % of it: DESIGN 4.14).  Lane 0 gets lane 63's, which
+// its caller replaces.
+__device__ __forceinline__ int from_lane_below(int v) {
+  return __builtin_amdgcn_update_dpp(0, v, 0x13C, 0xf, 0xf, false);
+}
+
+// The distances of the strip's 64 rows (32 unless `two`) against the 32 columns of a tile, into the ring at column
+// offset `c_off`.  `x0`, `x1`, `yc`: this lane's operand rows (lattice rows l & 31 and 32 + (l & 31), column l & 31).
+// The k loop goes in groups of 4 MFMA steps (8 k) whose 12 operand loads are issued one group ahead, before the
+// MFMAs of the group in hand: one wait per group instead of one per step.
+template <int METRIC, int S>
+__device__ __forceinline__ void make_tile(const float* __restrict__ x0, const float* __restrict__ x1,
+                                          const float* __restrict__ yc, const int dim, const bool two, const int lh,
+                                          const int li, const int c_off, const float ya, const float* xa,
+                                          float* ring) {
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.0f;
+  float a0[4], a1[4], b[4], na0[4], na1[4], nb[4];
+  auto load = [&](int g, float* A0, float* A1, float* B) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int k = 8 * g + 2 * s + lh;
+      const bool ok = k < dim;
+      B[s] = ok ? yc[k] : 0.0f;
+      A0[s] = ok ? x0[k] : 0.0f;
+      A1[s] = (ok && two) ? x1[k] : 0.0f;
+    }
+  };
+  const int groups = (dim + 7) >> 3;
+  load(0, a0, a1, b);
+  for (int g = 0; g < groups; ++g) {
+    if (g + 1 < groups) load(g + 1, na0, na1, nb);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (8 * g + 2 * s < dim) {   // (the same for the whole wave; an odd D: the last step's second k is zero)
+        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b[s], acc0, 0, 0, 0);
+        if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b[s], acc1, 0, 0, 0);
+      }
+    }
+    if (g + 1 < groups) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        a0[s] = na0[s];
+        a1[s] = na1[s];
+        b[s] = nb[s];
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int i = (r & 3) + 8 * (r >> 2) + 4 * lh;
+    ring[i * S + c_off + li] = frame_distance<METRIC>(acc0[r], xa[i], ya);
+  }
+  if (two) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      ring[i * S + c_off + li] = frame_distance<METRIC>(acc1[r], xa[i], ya);
+    }
+  }
+}
+
+template <int METRIC, int SLOTS, int SEAM>
+__global__ __launch_bounds__(64) void dtw_pairs_kernel(const float* __restrict__ rows, const int dim,
+                                                       const DtwItem* __restrict__ items,
+                                                       const DtwPair* __restrict__ pairs, const int64_t n_pairs,
+                                                       const float* __restrict__ aux, const int64_t row_lo,
+                                                       float* __restrict__ cost, int32_t* __restrict__ len) {
+  constexpr int S = 32 * SLOTS;
+  __shared__ float ring[64 * S];
+  __shared__ float xa[64];
+  __shared__ float2 seam[SEAM];
+  const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
+  const float inf = __builtin_inff();
+  for (int64_t p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+    const DtwPair pair = pairs[p];
+    const DtwItem ix = items[pair.x], iy = items[pair.y];
+    const int N = ix.frames, M = iy.frames;   // (1 <= N <= kDtwMaxFrames, 1 <= M <= SEAM: the host has checked)
+    const float* X = rows + ix.row0 * dim;
+    const float* Y = rows + iy.row0 * dim;
+    const float* ax = aux + (ix.row0 - row_lo);
+    const float* ay = aux + (iy.row0 - row_lo);
+    float C = 0.0f;
+    int L = 0;
+    for (int s0 = 0; s0 < N; s0 += 64) {
+      const int R = min(64, N - s0);
+      const bool more = s0 + 64 < N;
+      __syncthreads();   // (the last strip's reads of xa are done)
+      xa[lane] = ax[min(s0 + lane, N - 1)];
+      __syncthreads();
+      const float* x0 = X + static_cast<int64_t>(min(s0 + li, N - 1)) * dim;
+      const float* x1 = X + static_cast<int64_t>(min(s0 + 32 + li, N - 1)) * dim;
+      float dgC = inf;   // (C, L) of cell (i - 1, j - 1): what came from lane i - 1 one step earlier
+      int dgL = 0;
+      int pos = -lane;   // (t - lane) mod S once t >= lane
+      int slot = 0;      // (t / 32) mod SLOTS
+      const int steps = R + M - 1;
+      for (int t = 0; t < steps; ++t) {
+        if ((t & 31) == 0 && t < M) {   // (the same for the whole wave)
+          const int col = min(t + li, M - 1);
+          const float* yc = Y + static_cast<int64_t>(col) * dim;
+          const float ya = ay[col];
+          make_tile<METRIC, S>(x0, x1, yc, dim, R > 32, lh, li, 32 * slot, ya, xa, ring);
+          slot = slot + 1 == SLOTS ? 0 : slot + 1;
+          __syncthreads();
+        }
+        float upC = __builtin_bit_cast(float, from_lane_below(__builtin_bit_cast(int, C)));
+        int upL = from_lane_below(L);
+        if (lane == 0) {
+          upC = inf;
+          upL = 0;
+          if (s0 > 0 && t < M) {
+            const float2 above = seam[t];
+            upC = above.x;
+            upL = __builtin_bit_cast(int, above.y);
+          }
+        }
+        const int j = t - lane;
+        if (j >= 0 && j < M && lane < R) {
+          const float d = ring[lane * S + pos];
+          float bestC = j > 0 ? dgC : inf;
+          int bestL = dgL;
+          if (upC < bestC) {
+            bestC = upC;
+            bestL = upL;
+          }
+          if (j > 0 && C < bestC) {
+            bestC = C;
+            bestL = L;
+          }
+          const bool origin = s0 + lane == 0 && j == 0;
+          C = origin ? d : d + bestC;
+          L = origin ? 1 : bestL + 1;
+          dgC = upC;
+          dgL = upL;
+          if (more && lane == 63) seam[j] = make_float2(C, __builtin_bit_cast(float, L));
+        }
+        pos = pos + 1 == S ? 0 : pos + 1;
+      }
+      if (!more && lane == R - 1) {
+        cost[pair.out] = C;
+        len[pair.out] = L;
+      }
+    }
+  }
+}
+
+template <int METRIC, int CLASS>
+void launch_class(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs, int64_t n,
+                  const float* d_aux, int64_t row_lo, int compute_units, float* cost, int32_t* len,
+                  hipStream_t stream) {
+  if (n <= 0) return;
+  const int64_t waves = static_cast<int64_t>(compute_units) * kWavesPerCu[CLASS];
+  const dim3 grid(static_cast<unsigned>(n < waves ? n : waves)), block(64);
+  hipLaunchKernelGGL((dtw_pairs_kernel<METRIC, CLASS == 0 ? 1 : 3, kSeam[CLASS]>), grid, block, 0, stream, rows, dim,
+                     d_items, d_pairs, n, d_aux, row_lo, cost, len);
+}
+
+template <int METRIC>
+void launch_metric(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
+                   const int64_t* class_count, const float* d_aux, int64_t row_lo, int compute_units, float* cost,
+                   int32_t* len, hipStream_t stream) {
+  // the long pairs first: the short ones fill the compute units that they leave idle at their end
+  const DtwPair* p1 = d_pairs + class_count[0];
+  const DtwPair* p2 = p1 + class_count[1];
+  launch_class<METRIC, 2>(rows, dim, d_items, p2, class_count[2], d_aux, row_lo, compute_units, cost, len, stream);
+  launch_class<METRIC, 1>(rows, dim, d_items, p1, class_count[1], d_aux, row_lo, compute_units, cost, len, stream);
+  launch_class<METRIC, 0>(rows, dim, d_items, d_pairs, class_count[0], d_aux, row_lo, compute_units, cost, len,
+                          stream);
+}
+
+}  // namespace
+
+int launch_dtw_pairs(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
+                     const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
+                     int compute_units, float* cost, int32_t* len, hipStream_t stream) {
+  const int64_t n_rows = row_hi - row_lo;
+  if (n_rows <= 0) return SNF_OK;
+  hipLaunchKernelGGL(dtw_rows_kernel, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, stream, rows,
+                     dim, row_lo, n_rows, metric, d_aux);
+  SNF_HIP_CHECK(hipGetLastError());
+  if (metric == SNF_DTW_COSINE)
+    launch_metric<SNF_DTW_COSINE>(rows, dim, d_items, d_pairs, class_count, d_aux, row_lo, compute_units, cost, len,
+                                  stream);
+  else
+    launch_metric<SNF_DTW_SQEUCLIDEAN>(rows, dim, d_items, d_pairs, class_count, d_aux, row_lo, compute_units, cost,
+                                       len, stream);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+}  // namespace snf

@@ -365,6 +365,26 @@ int launch_collate_padded(const float* in, const CollateUtt* d_utts, const Colla
 int launch_sliding_cmvn(const snf_sliding_cmvn_options& o, const float* in, int in_cols,
                         const int64_t* frame_offsets, int64_t n_utts, float* out,
                         hipStream_t stream);
+// kernels_dtw.hip: DTW cost and path length of pairs of items (snf_dtw_pairs)
+constexpr int kDtwMaxFrames = 4096;   // rows of an item: the seam row of the largest kernel class holds as many columns
+constexpr int kDtwMaxDim = 4096;
+constexpr int kDtwClasses = 3;        // kernel classes by the columns M of a pair: M <= 32, <= 512, <= kDtwMaxFrames
+struct DtwItem {
+  int64_t row0;     // first row of the item in the block
+  int32_t frames;   // its rows
+  int32_t unused;
+};
+struct DtwPair {
+  int32_t x, y;     // item indices: x gives the rows of the lattice, y its columns
+  int32_t out;      // where the result goes (the caller's pair order)
+  int32_t cells;    // frames(x) frames(y): the sort key
+};
+int dtw_class_of(int32_t columns);
+// `d_pairs`: the pairs of class 0, then 1, then 2 (`class_count` of each), each class sorted by cells descending;
+// `d_aux`: one float per row of [row_lo, row_hi), written by the pre-pass
+int launch_dtw_pairs(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
+                     const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
+                     int compute_units, float* cost, int32_t* len, hipStream_t stream);
 
 struct PitchPostParams {
   snf_pitch_post_options o;

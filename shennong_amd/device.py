@@ -213,6 +213,31 @@ class DeviceFeaturesCollection(dict):
             self[name] = made[name]
         return self
 
+    @classmethod
+    def from_host(cls, collection, device=None):
+        """The host :class:`FeaturesCollection` `collection` (features read from a file, say) as a device
+        collection in ONE block, uploaded once (``_backend.upload_rows``); ``to_host()`` of the result gives equal
+        Features.  ValueError, before any device work, for utterances of different `ndims` and for data that is
+        not a float32 matrix."""
+        names = list(collection)
+        for name in names:
+            data = collection[name].data
+            if not isinstance(data, np.ndarray) or data.ndim != 2 or data.dtype != np.float32:
+                raise ValueError(f'utterance "{name}": data must be a float32 matrix [nframes, ndims]')
+        dims = sorted({collection[name].ndims for name in names if collection[name].nframes})
+        if len(dims) > 1:
+            raise ValueError('utterances have different ndims: {}'.format(dims))
+        dim = dims[0] if dims else (collection[names[0]].ndims if names else 0)
+        template = FeaturesCollection()
+        for name in names:
+            host = collection[name]
+            shape = host.data.shape
+            placeholder = np.broadcast_to(np.float32(0), shape) if shape[0] else np.zeros(shape, dtype=np.float32)
+            template[name] = Features._of_batch(placeholder, host._times_view(), host.properties, None)
+        mats = [collection[name].data for name in names if collection[name].nframes]
+        buffer = _backend.upload_rows(mats, np.float32, device)
+        return cls._build(template, [(buffer, names, dim)])
+
     def _alive(self):
         for block in self._blocks:
             block.alive()
