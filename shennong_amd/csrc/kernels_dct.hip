@@ -117,7 +117,8 @@ int launch_mfcc_dct(const float* in, int in_cols, int num_bins, int num_ceps, co
   if (total_frames <= 0) return SNF_OK;
   const int num_ceps8 = (num_ceps + 15) & ~15;
   const int in_pitch = in_cols | 1;   // an odd row pitch: a lane per row, no bank conflict
-  // one workgroup per CU, as many waves as tiles fit beside the matrix in its LDS (14 for 40 bins + energy)
+  // one workgroup per CU, as many waves as tiles fit beside the matrix in its LDS (10 for 40 bins + energy and
+  // 40 cepstra, 5 for 80 bins + energy and 40 cepstra)
   const size_t dt_bytes = sizeof(float) * (((static_cast<size_t>(num_bins) * num_ceps8 + 3) & ~static_cast<size_t>(3)) + num_ceps8);
   const size_t tile_bytes = sizeof(float) * 64 * static_cast<size_t>(in_pitch + 17);
   const size_t budget = 159 * 1024;

@@ -1185,6 +1185,7 @@ int launch_vad(const snf_vad_options& o, const float* in, int in_cols, const int
   if (total_frames <= 0) return SNF_OK;
   hipLaunchKernelGGL(vad_threshold_kernel, dim3(static_cast<unsigned>(n_utts)), dim3(256), 0, stream,
                      o, in, in_cols, frame_offsets, thr_scratch);
+  SNF_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(vad_kernel, dim3(static_cast<unsigned>((total_frames + 255) / 256)), dim3(256),
                      0, stream, o, in, in_cols, frame_offsets, n_utts, total_frames, thr_scratch, out);
   SNF_HIP_CHECK(hipGetLastError());
@@ -1319,7 +1320,8 @@ int launch_cmvn_apply(const float* in, int in_cols, const int64_t* frame_offsets
 }
 
 // Sliding-window CMN ([KALDI-UPSTREAM] feat/feature-functions.cc SlidingWindowCmnInternal): one thread
-// per (utterance, column) walks the frames with Kaldi's incremental double-precision window sums.
+// per (utterance, column) walks the frames with Kaldi's incremental double-precision window sums (the mean
+// leaves the frame as one correctly rounded quotient: see below).
 __global__ void sliding_cmvn_kernel(const snf_sliding_cmvn_options o, const float* __restrict__ in,
                                     const int D, const int64_t* __restrict__ frame_offsets,
                                     const int64_t n_utts, float* __restrict__ out) {
@@ -1360,7 +1362,11 @@ __global__ void sliding_cmvn_kernel(const snf_sliding_cmvn_options o, const floa
     const int64_t wf = we - ws;
     last_start = ws;
     last_end = we;
-    double r = static_cast<double>(x[t * D]) + (-1.0 / static_cast<double>(wf)) * cur_sum;
+    // x - S / wf, the quotient rounded once: Kaldi's AddVec(-1.0 / wf, S) rounds -1 / wf first, which leaves
+    // x 2^-53 behind on a column that is constant over the window (S = wf x, exactly) - and 1e5 times that where
+    // the variance floor takes over.  The division returns x itself there, the difference is the literal 0;
+    // elsewhere the two forms differ by at most one rounding of the mean, far below the float32 result's own.
+    double r = static_cast<double>(x[t * D]) - cur_sum / static_cast<double>(wf);
     if (o.normalize_variance) {
       if (wf == 1) r = 0.0;
       else {
@@ -1430,7 +1436,10 @@ int launch_concat_columns(const float* a, int cols_a, const int64_t* d_off_a, co
 
 // Features.validate's data check (reference features.py:170-215 `is_valid`: "data contains non-finite
 // numbers") for a block that is still in HBM: the number of NaN / +-Inf among n floats.  An exponent
-// field of all ones is the test; 16-byte loads over the aligned body, one atomic per workgroup.
+// field of all ones is the test; 16-byte loads over the aligned body, the 0 - 3 floats behind it by the first
+// lanes of workgroup 0.  A wave none of whose lanes saw a bad value adds nothing; in any other wave EVERY lane
+// executes the atomic add with its own count (zeros included): one atomic per lane of such a wave as written,
+// not one per workgroup - there is no reduction across the waves of a workgroup - and none in the usual case.
 __global__ void __launch_bounds__(256) count_nonfinite_kernel(const float* __restrict__ x, uint64_t n,
                                                               unsigned long long* __restrict__ count) {
   const uint64_t n4 = n >> 2;

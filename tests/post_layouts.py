@@ -2,7 +2,12 @@
 test_post_routes_gpu.py): lists of utterance lengths whose concatenation, cut into tiles of R rows, puts an
 utterance boundary on every kind of tile seam.  The tile heights are restated here, not read from the source:
 a change of kernels_post.hip that moves a seam has to be made here too, and `check_seams` then says what the
-layouts no longer reach."""
+layouts no longer reach.
+
+The second half holds the layouts and restated launch arithmetic of the remaining kernels of the path
+(test_post_remaining.py, test_post_remaining_gpu.py): the 256-thread stride loop of vad_threshold_kernel, the 64
+threads per workgroup of sliding_cmvn_kernel, the 32-row tiles of concat_columns_kernel, the capped grid of
+count_nonfinite_kernel and the waves, workgroups and tiles of mfcc_dct_kernel (kernels_dct.hip)."""
 
 import numpy as np
 
@@ -75,13 +80,18 @@ def seam_layout(rows):
     last tile   partial with an odd number of rows, then an empty utterance"""
     if rows < 36:
         raise ValueError('the layouts are written for tiles of 36 rows or more')
+    return check_seams(_seam_lengths(rows), rows)
+
+
+def _seam_lengths(rows):
+    """the lengths of `seam_layout`, unchecked (rows >= 32: the first seam's utterances need 12 + 3 rows below it)"""
     lengths = [0, 1, 2, 3, 1, 1, 1, 0, 1, 1, 1]              # 12 rows
     lengths += [rows - 3 - 12, 2, 3, 2]                      # ends rows-3, rows-1, rows+2, rows+4
     lengths += [4 * rows - (rows + 4)]                       # ... 4 rows: exactly on the seam
     lengths += [rows - 4, 2, 3, 2]                           # ends 5 rows -4, -2, +1, +3
     tail = (rows // 2) & ~1                                  # 3 + tail rows in the last tile: odd
     lengths += [tail, 0]
-    return check_seams(lengths, rows)
+    return lengths
 
 
 def seam_layout_small():
@@ -141,3 +151,217 @@ def cmvn_lengths(cols):
     """utterance lengths around the R = 256 // cols rows that cmvn_stats_kernel reduces in parallel"""
     r = max(1, 256 // cols)
     return [0, 1, r - 1, r, r + 1, 1000]
+
+
+# ---- the remaining kernels of the same path (test_post_remaining.py, test_post_remaining_gpu.py) ------------------
+VAD_THREADS = 256        # vad_threshold_kernel: one workgroup of 256 threads per utterance, `t += blockDim.x`
+SLIDING_THREADS = 64     # sliding_cmvn_kernel: one thread per (utterance, column), 64 per workgroup
+CONCAT_ROWS = 32         # kConcatRows: output rows per workgroup of concat_columns_kernel
+NONFINITE_THREADS = 256  # count_nonfinite_kernel: 256 threads, 4 floats each, at most ...
+NONFINITE_MAX_BLOCKS = 4096   # ... 256 * 16 workgroups (launch_count_nonfinite)
+
+
+def check_vad_passes(lengths):
+    """the utterance lengths around the 256-thread stride loop of vad_threshold_kernel: zero, one and two extra
+    passes, a partial wave in the last one, an utterance of many passes, empty utterances at the head, inside and
+    at the tail"""
+    lengths = [int(n) for n in lengths]
+    missing = [str(n) for n in (VAD_THREADS - 1, VAD_THREADS, VAD_THREADS + 1, 2 * VAD_THREADS + 1, 1, 2, 3)
+               if n not in lengths]
+    if max(lengths) <= 2 * VAD_THREADS + 1:
+        missing.append('an utterance longer than 513 frames')
+    if lengths[0] or lengths[-1] or 0 not in lengths[1:-1]:
+        missing.append('empty utterances at the head, inside and at the tail')
+    if missing:
+        raise ValueError(f'VAD layout {lengths} lacks: {", ".join(missing)}')
+    return lengths
+
+
+def vad_layout():
+    """`seam_layout(256)` - about 1 400 frames, a 764-frame utterance, empty utterances at the head, in the middle
+    and at the tail, lengths 1, 2 and 3 - with utterances of 255, 256, 257 and 513 frames in front of its last,
+    empty, one"""
+    base = seam_layout(VAD_THREADS)
+    return check_vad_passes(base[:-1] + [VAD_THREADS - 1, VAD_THREADS, VAD_THREADS + 1, 2 * VAD_THREADS + 1] + base[-1:])
+
+
+# (frames_context, energy_mean_scale, proportion_threshold, energy_threshold); the columns are crossed with them
+# (a context of 300 frames with half of the energies above the threshold: a proportion of 0.5 keeps the flags mixed)
+VAD_OPTIONS = [(0, 0.5, 0.6, 5.0), (2, 0.5, 0.6, 5.0), (300, 0.5, 0.5, 5.0), (2, 0.0, 0.6, 10.0),
+               (0, 0.5, 0.5, 5.0), (2, 0.5, 0.25, 5.0), (300, 0.0, 0.5, 10.0)]
+VAD_COLS = (1, 13, 40)
+# the exact-arithmetic cases: (frames_context, proportion_threshold)
+VAD_TIES = [(0, 0.5), (2, 0.6), (2, 0.25), (0, 0.6)]
+
+# (cmn_window, min_window) of the sliding-window CMVN cases: even; odd and centred; min_window > cmn_window;
+# larger than every utterance
+SLIDING_WINDOWS = [(40, 40), (41, 10), (7, 50), (600, 100)]
+SLIDING_COLS = (1, 13, 64, 257)
+
+
+SLIDING_CASES = [(w, c, v) for w in SLIDING_WINDOWS for c in (True, False) for v in (False, True)]
+
+
+def sliding_id(case):
+    (cmn, minw), center, nv = case
+    return f'w{cmn}-m{minw}-{"centre" if center else "left"}-{"var" if nv else "mean"}'
+
+
+def sliding_lengths(cmn_window, min_window):
+    """0, 1, 2, 3, cmn_window - 1, cmn_window, cmn_window + 1, min_window - 1, min_window + 1 and
+    2 cmn_window + 5 frames, the empty utterances at the head, in the middle and at the tail of the batch"""
+    return [0, 1, 2, 3, cmn_window - 1, cmn_window, 0, cmn_window + 1, min_window - 1, min_window + 1,
+            2 * cmn_window + 5, 0]
+
+
+def sliding_five(cmn_window, min_window):
+    """five utterances, none empty: with 13 columns 65 threads, the last one alone in a second workgroup"""
+    return [3, cmn_window + 1, 1, min_window + 1, 2]
+
+
+def check_sliding(lengths, cmn_window, min_window):
+    lengths = [int(n) for n in lengths]
+    need = {0, 1, 2, 3, cmn_window - 1, cmn_window, cmn_window + 1, min_window - 1, min_window + 1,
+            2 * cmn_window + 5}
+    missing = sorted(need - set(lengths))
+    if lengths[0] or lengths[-1] or 0 not in lengths[1:-1]:
+        missing.append('empty utterances at the head, inside and at the tail')
+    if missing:
+        raise ValueError(f'sliding layout {lengths} lacks: {missing}')
+    return lengths
+
+
+def sliding_threads(lengths, cols):
+    """(threads, workgroups, threads of the last workgroup, True when some workgroup holds columns of two utterances
+    in one wave) of launch_sliding_cmvn"""
+    threads = len(lengths) * cols
+    blocks = (threads + SLIDING_THREADS - 1) // SLIDING_THREADS
+    inside = any((u * cols) % SLIDING_THREADS for u in range(1, len(lengths)))
+    return threads, blocks, threads - (blocks - 1) * SLIDING_THREADS, inside
+
+
+# (cols_a, cols_b) of the concatenation cases: 32 (ca + cb) a multiple of 256 and not
+CONCAT_COLS = [(1, 1), (13, 3), (40, 2), (3, 13), (257, 2), (2, 257)]
+CONCAT_TRIM = [(0, 0), (2, 0), (0, 3), (1, 5), (4, 1)]   # rows that (a, b) hold beyond the output, by utterance % 5
+
+
+def concat_layout():
+    """(rows of the output, of a, of b) per utterance: the output is `seam_layout`'s list at 32 rows per tile - every
+    seam of check_seams, empty utterances included -, a and b are longer by CONCAT_TRIM, so that the input offsets
+    drift away from the output offsets"""
+    out = check_seams(_seam_lengths(CONCAT_ROWS), CONCAT_ROWS)
+    a = [n + CONCAT_TRIM[u % len(CONCAT_TRIM)][0] for u, n in enumerate(out)]
+    b = [n + CONCAT_TRIM[u % len(CONCAT_TRIM)][1] for u, n in enumerate(out)]
+    return out, a, b
+
+
+def check_concat(out, a, b):
+    """some utterances with a longer than the output, some with b longer, some with both, some with neither; an
+    empty output with rows in a or b; the offsets of a and of b differ from the output's from the second tile on"""
+    kinds = {(x > n, y > n) for n, x, y in zip(out, a, b)}
+    missing = [str(k) for k in ((False, False), (True, False), (False, True), (True, True)) if k not in kinds]
+    if any(x < n or y < n for n, x, y in zip(out, a, b)):
+        missing.append('an input shorter than the output')
+    if not any(n == 0 and (x or y) for n, x, y in zip(out, a, b)):
+        missing.append('an empty output of a non-empty input')
+    oo, oa, ob = offsets_of(out), offsets_of(a), offsets_of(b)
+    late = [u for u in range(len(out)) if oo[u] >= CONCAT_ROWS and out[u]]
+    if not late or any(oa[u] == oo[u] or ob[u] == oo[u] or oa[u] == ob[u] for u in late):
+        missing.append('drifting offsets')
+    if missing:
+        raise ValueError(f'concat layout lacks: {", ".join(missing)}')
+    return out, a, b
+
+
+# sizes of the non-finite count: the tail alone, body + tail, and the capped grid
+NONFINITE_GRID = 4 * NONFINITE_THREADS * NONFINITE_MAX_BLOCKS           # floats one pass of the capped grid reads
+NONFINITE_SIZES = [1, 2, 3, 4, 5, 7, 1024, 1025, 1027, NONFINITE_GRID + 3]
+# NONFINITE_GRID + 3 = 4 194 307 fills the capped grid exactly ONCE (see nonfinite_launch): a second pass needs
+# more than NONFINITE_GRID / 4 vectors.  This size gives workgroups 0 and 1 a second pass, and a tail of 3
+NONFINITE_SECOND_PASS = NONFINITE_GRID + 4 * (NONFINITE_THREADS + 1) + 3
+
+
+def nonfinite_launch(n):
+    """launch_count_nonfinite restated: (workgroups, vectors of 4 floats, passes of the stride loop that thread 0
+    of workgroup 0 makes, floats of the tail)"""
+    n4 = n // 4
+    blocks = min(max((n4 + NONFINITE_THREADS - 1) // NONFINITE_THREADS, 1), NONFINITE_MAX_BLOCKS)
+    stride = blocks * NONFINITE_THREADS
+    return blocks, n4, (n4 + stride - 1) // stride, n % 4
+
+
+def nonfinite_places(n):
+    """indices worth a lone non-finite value: element 0, the last of the vector body, every tail element, and the
+    first elements a thread reaches in its second pass (workgroups 0 and 1)"""
+    blocks, n4, passes, tail = nonfinite_launch(n)
+    places = {0, n - 1}
+    if n4:
+        places.add(4 * n4 - 1)
+    places.update(range(4 * n4, n))
+    if passes > 1:
+        stride = blocks * NONFINITE_THREADS
+        places.update(4 * v + k for v in (stride, stride + NONFINITE_THREADS) if v < n4 for k in (0, 3))
+    return sorted(places)
+
+
+# ---- mfcc_dct_kernel: launch_mfcc_dct restated --------------------------------------------------------------------
+MFCC_DCT_LDS = 159 * 1024
+MFCC_DCT_MAX_BLOCKS = 256
+
+
+def mfcc_dct_launch(num_bins, num_ceps, use_energy, total_frames):
+    """(waves per workgroup, frames per workgroup, workgroups, largest number of 64-frame tiles one wave takes)"""
+    in_cols = num_bins + (1 if use_energy else 0)
+    in_pitch = in_cols | 1
+    ceps16 = (num_ceps + 15) & ~15
+    dt_bytes = 4 * (((num_bins * ceps16 + 3) & ~3) + ceps16)
+    tile_bytes = 4 * 64 * (in_pitch + 17)
+    n_waves = min((MFCC_DCT_LDS - dt_bytes) // tile_bytes, 16)
+    tiles = (total_frames + 63) // 64
+    blocks = min((tiles + n_waves - 1) // n_waves, MFCC_DCT_MAX_BLOCKS)
+    per_wave = (tiles + blocks * n_waves - 1) // (blocks * n_waves)
+    return n_waves, 64 * n_waves, blocks, per_wave
+
+
+MFCC_UTT_FRAMES = 77          # one utterance of the first batches: 64 + 13 frames at the default shift of 160 samples
+MFCC_UTT_SAMPLES = 400 + (MFCC_UTT_FRAMES - 1) * 160
+# (MfccProcessor options, copies of the utterance): batches just past ONE workgroup's frames
+MFCC_FIRST = [
+    (dict(num_bins=40, num_ceps=40), 9),
+    (dict(num_bins=40, num_ceps=40, use_energy=False), 9),
+    (dict(num_bins=40, num_ceps=40, cepstral_lifter=0.0), 9),
+    (dict(num_bins=40, num_ceps=17, htk_compat=True), 9),
+    (dict(num_bins=40, num_ceps=24, htk_compat=True, use_energy=False), 9),
+    (dict(num_bins=40, num_ceps=33, htk_compat=True), 9),
+    (dict(num_bins=40, num_ceps=33, htk_compat=True, use_energy=False, cepstral_lifter=0.0), 9),
+    (dict(num_bins=80, num_ceps=40), 5),
+    (dict(num_bins=80, num_ceps=40, htk_compat=True, use_energy=False), 5),
+]
+# the batch past 256 workgroups: 80 bins, 40 cepstra (5 waves: 256 x 5 x 64 = 81 920 frames in one pass); a frame
+# shift of 32 samples keeps the audio at 26 640 samples per utterance
+MFCC_BIG = (dict(num_bins=80, num_ceps=40, frame_shift=0.002), 101)
+MFCC_BIG_FRAMES = 821
+# synth.utterances ids of the two utterances.  The float32 oracle is a coarse judge of 80-bin cepstra: a narrow low
+# mel bin on a spectral null carries a float32 error that the lifter (up to 12 x) amplifies, and on most 821-frame
+# utterances the ORACLE is further from the float64 statement than the family tolerance allows the device to be
+# from the oracle.  The big utterance is the one of MFCC_BIG_CANDIDATES on which the oracle is closest to the
+# float64 statement - a choice that looks at the reference alone (test_post_remaining.py recomputes it).
+MFCC_UTT_ID = 500
+MFCC_BIG_CANDIDATES = range(501, 521)
+MFCC_BIG_ID = 512
+MFCC_BIG_SAMPLES = 400 + (MFCC_BIG_FRAMES - 1) * 32
+
+
+def mfcc_id(case):
+    opts, copies = case
+    return '-'.join(f'{k}{v}' for k, v in opts.items()) + f'-x{copies}'
+
+
+def mfcc_energy(opts):
+    return bool(opts.get('use_energy', True))
+
+
+def fbank_options(opts):
+    """the options of the FilterbankProcessor whose rows an MFCC plan's scratch holds: [log energy |] log-mel"""
+    keep = {k: v for k, v in opts.items() if k not in ('num_ceps', 'cepstral_lifter', 'htk_compat', 'use_energy')}
+    return dict(keep, use_energy=mfcc_energy(opts), htk_compat=False, use_log_fbank=True, use_power=True)
