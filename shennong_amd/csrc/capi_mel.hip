@@ -182,7 +182,7 @@ int prepare_mel_tables(MelCall* c, const int64_t* sample_offsets, const int64_t*
   const int64_t n_utts = b.n_utts, total_frames = b.total_frames;
   int rc;
   if (r.blocks) {
-    const int kSetsPerBlock = r.fused ? kFast512FusedSets : 64;  // (kernels_fbank512.hip)
+    const int kSetsPerBlock = r.fused ? kFast512FusedSets : kFast512Sets;  // (fbank512_kernel: sets_per_block)
     std::vector<int32_t> blk_utt, blk_set0;
     for (int64_t u = 0; u < n_utts; ++u) {
       if (r.fe == FrontEnd::dual256_split && warp_ids[u] == 0) continue;  // (runs on fbank256x2_kernel)

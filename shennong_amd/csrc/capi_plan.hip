@@ -286,8 +286,7 @@ int choose_fast_path(snf_plan* plan) {
       plan->fast512 = true;
       if (want_fused) {
         // (the fused form keeps 14 waves' tiles + the cepstra of 336 frames in LDS beside the tables)
-        if (((static_cast<size_t>(plan->fp.table_floats) * 4 + 255) & ~static_cast<size_t>(255)) +
-                14 * 4 * 2176 + sizeof(float) * 4 * (kFast512FusedSets + 2) * 16 > 160 * 1024)
+        if (fast512_lds_bytes(plan->fp.table_floats, kFast512FusedWaves, true) > kFast512LdsBytes)
           return set_error(SNF_E_INVALID, "append_deltas: the mel / DCT tables of this configuration leave no "
                                           "room for the fused form in LDS; chain a delta plan");
         plan->fp.fused_delta = 1;

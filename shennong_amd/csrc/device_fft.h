@@ -1,5 +1,5 @@
-// Device helpers shared by the register-resident FFT kernels (kernels_fbank512.hip, kernels_fbank512b.hip and,
-// through device_fft1024.h, kernels_fbank2048.hip and kernels_fbank1024x2.hip):
+// Device helpers shared by the register-resident FFT kernels (kernels_fbank512.hip, kernels_fbank256x2.hip,
+// kernels_fbank512b.hip and, through device_fft1024.h, kernels_fbank2048.hip and kernels_fbank1024x2.hip):
 // LDS access wrappers, DPP reductions, the counter-based dither generator and the 16-point register FFT.
 // Included inside namespace snf; everything is static to the including translation unit.
 #ifndef SNF_DEVICE_FFT_H_

@@ -41,10 +41,11 @@ namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kWaves = 16;          // one 16-wave workgroup per CU (4 waves per SIMD)
-constexpr int kHeaderFloats = 16;   // (= kFastHeaderFloats of kernels_fbank512.hip: same table blob)
-constexpr int kTileRow = 17;        // complex per row of the exchange tile (16 + 1 pad: conflict-free)
-constexpr int kTileBytes = 16 * kTileRow * 8;  // wave-private LDS per frame (2176 B)
+// the LDS layout of the family (snf_internal.h: same table blob, same tiles) under the names the kernel body uses
+constexpr int kWaves = kFast512MaxWaves;          // one 16-wave workgroup per CU (4 waves per SIMD)
+constexpr int kHeaderFloats = kFast512HeaderFloats;
+constexpr int kTileRow = kFast512TileRow;         // complex per row of the exchange tile
+constexpr int kTileBytes = kFast512TileBytes;     // wave-private LDS per frame
 
 
 }  // namespace
@@ -604,7 +605,7 @@ bool fbank512b_shape_ok(const Fast512Params& p, bool per_utt) {
   if (!p.snip_edges || p.dct_mfma) return false;
   // (the spectrogram's four 16-byte row stores per lane measured 7 % slower here than on fbank512_kernel)
   if (p.kind != SNF_KIND_FBANK && p.kind != SNF_KIND_MFCC && p.kind != SNF_KIND_PLP) return false;
-  return static_cast<size_t>((p.table_floats * 4 + 255) & ~255) + kWaves * 4 * kTileBytes <= 160 * 1024;
+  return fast512_lds_bytes(p.table_floats, kWaves, false) <= kFast512LdsBytes;
 }
 bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b) {
   if (p.dither != 0.0f && b.frame_noise == nullptr) return false;  // (no key table: fbank512_kernel draws its own)
@@ -615,7 +616,7 @@ namespace {
 
 template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV>
 int launch_dither(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
-  const size_t lds = static_cast<size_t>((q.table_floats * 4 + 255) & ~255) + kWaves * 4 * kTileBytes;
+  const size_t lds = fast512_lds_bytes(q.table_floats, kWaves, false);
   const int64_t n_sets = (b.total_frames + 3) / 4;
   int64_t blocks = (n_sets + kWaves - 1) / kWaves;
   if (blocks > 256) blocks = 256;  // one resident workgroup per CU, grid-stride over the frame sets

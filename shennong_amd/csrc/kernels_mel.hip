@@ -7,7 +7,8 @@
 // runs out of a wave-private LDS region, so a frame makes exactly one trip from HBM (int16 samples
 // in, float32 features out) and no workgroup barrier is ever needed.  This kernel handles every
 // option combination (any window length / FFT size / window type / snip_edges / VTLN warp);
-// kernels_fbank512.hip specialises the headline 25 ms / 16 kHz (512-point) configuration.
+// kernels_fbank512.hip, kernels_fbank512b.hip and kernels_fbank256x2.hip specialise the frames that pad to
+// 512 samples or fewer (the headline 25 ms / 16 kHz configuration among them).
 //
 // Restates [KALDI-UPSTREAM] feature-window.cc (ExtractWindow / ProcessWindow), feature-fbank.cc,
 // feature-mfcc.cc, feature-spectrogram.cc, mel-computations.cc (MelBanks::Compute), which the

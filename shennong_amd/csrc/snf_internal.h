@@ -212,9 +212,30 @@ int launch_deltas(const DeltaParams& p, const float* in, int in_cols, const int6
                   hipStream_t stream, const char** launched = nullptr);
 
 
-// ---- register-resident 512-point fast path (kernels_fbank512.hip) ----------------------------------
+// ---- register-resident 512-point fast path: fbank512_kernel (kernels_fbank512.hip), fbank256x2_kernel
+// (kernels_fbank256x2.hip), fbank512b_kernel (kernels_fbank512b.hip); their tables: fast512_tables.cpp ----
 constexpr int kFast512MaxBins = 64;    // mel bins: 16 MFMA blocks of 4 bins
-constexpr int kFast512FusedSets = 82;  // fused deltas: frame sets per workgroup (kernels_fbank512.hip)
+// The LDS of a workgroup, stated once for the kernels, their launchers and the admission checks of the host
+// layer: [table blob, rounded up to 256 bytes | waves x 4 frame tiles | fused deltas: cepstra of the
+// workgroup's frame sets and one halo set on each side].
+constexpr int kFast512HeaderFloats = 16;  // table header: the mel layout of one warp factor
+constexpr int kFast512TileRow = 17;       // complex per transposed row (16 + 1 pad: conflict-free)
+constexpr int kFast512TileBytes = 16 * kFast512TileRow * 8;  // wave-private LDS per frame (2176 B)
+constexpr int kFast512MaxWaves = 16;    // wavefronts per workgroup: 8 when two workgroups fit the LDS of a CU
+constexpr int kFast512MinWaves = 8;     // (measured 5 % faster), else one of 16
+constexpr int kFast512FusedWaves = 14;  // fused deltas: 14 waves x 6 sets = 82 sets + one halo set on each side
+constexpr int kFast512FusedSets = 82;   // (the +-4 frames the delta-delta reaches); a 3 s utterance (75 sets) is
+                                        // one workgroup without any halo
+constexpr int kFast512Sets = 64;        // per-utterance schedule: frame sets (of 4 frames) per workgroup
+constexpr int kFast512FusedCols = 16;   // cepstra per row of the fused form's LDS buffer (num_ceps <= 16)
+constexpr size_t kFast512LdsBytes = 160 * 1024;  // LDS of a CU
+constexpr size_t fast512_table_bytes(int table_floats) {
+  return (static_cast<size_t>(table_floats) * 4 + 255) & ~static_cast<size_t>(255);
+}
+constexpr size_t fast512_lds_bytes(int table_floats, int waves, bool fused) {
+  return fast512_table_bytes(table_floats) + static_cast<size_t>(waves) * 4 * kFast512TileBytes +
+         (fused ? sizeof(float) * 4 * (kFast512FusedSets + 2) * kFast512FusedCols : 0);
+}
 struct Fast512Params {
   int win_len, win_shift, remove_dc, snip_edges;
   float preemph, dither;
@@ -259,6 +280,10 @@ int launch_build_frame_start(const int64_t* d_frame_offsets, const int64_t* d_sa
 // fbank512_kernel; nullptr: none)
 int launch_fbank512(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
                     double* energy_out, hipStream_t stream, const char** launched = nullptr);
+// the two-frames-per-row half of launch_fbank512 (kernels_fbank256x2.hip; `p.dual` tables, `b` carries the
+// pair table): the launch over the pairs and, with a fix-up list, the one over the pairs it put down
+int launch_fbank256x2(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
+                      double* energy_out, hipStream_t stream);
 // per-call table of the frames' noise keys (wave_noise_id: the dither of fbank512b_kernel; the keys hold
 // the first two samples of the utterance, so they are rebuilt with every batch)
 int launch_build_frame_noise(const BatchArgs& b, uint64_t* d_keys, hipStream_t stream);

@@ -698,6 +698,31 @@ def test_fast_kernel_vtln(gpu, synth_waves, cls, snip_edges):
         assert f.properties[proc.name]['vtln_warp'] == wf
 
 
+@pytest.mark.parametrize('cls, sample_rate, warps, kernel', [
+    (FilterbankProcessor, 16000, None, 'fbank512_kernel'),          # flat schedule (SNF_FBANK512_OLD keeps it there)
+    (MfccProcessor, 16000, [0.9, 1.0, 1.15], 'fbank512_kernel'),    # per-utterance schedule
+    (FilterbankProcessor, 8000, None, 'fbank256x2_kernel'),         # two frames per row and its fix-up launch
+])
+def test_fast512_eight_wave_workgroups(gpu, monkeypatch, cls, sample_rate, warps, kernel):
+    """the 8-wave geometry of the two launchers: no table of today leaves room for two workgroups per CU, so
+    only the SNF_FAST512_WAVES knob reaches it.  Utterances of 1, 9 and 10 frames (an odd last frame paired with
+    itself, an odd pair count); the features must match the oracle and, bit for bit, the 16-wave launch"""
+    shift, length = sample_rate // 100, sample_rate // 40
+    waves = [synth.utterances(51 + i, 1, length + shift * k, sample_rate)[0] for i, k in enumerate((0, 8, 9))]
+    audios = [Audio(w, sample_rate) for w in waves]
+    proc = cls(sample_rate=sample_rate, dither=0)
+    kw = dict(vtln_warp=warps) if warps else {}
+    monkeypatch.setenv('SNF_FBANK512_OLD', '1')
+    wide = [f.data for f in proc._process_batch(audios, **kw)]
+    monkeypatch.setenv('SNF_FAST512_WAVES', '8')
+    feats = proc._process_batch(audios, **kw)
+    assert _backend.get_plan(proc._build_options()).kernel_name(1) == kernel
+    assert [f.shape[0] for f in feats] == [1, 9, 10]
+    for w, wf, f, f16 in zip(waves, warps or [1.0] * 3, feats, wide):
+        assert_close(f.data, _oracle(proc, w, wf), rtol=1e-4, what=f'{proc.name} {sample_rate} Hz, 8 waves')
+        assert np.array_equal(f.data, f16)
+
+
 @pytest.mark.parametrize('snip_edges', [True, False])
 @pytest.mark.parametrize('cls, sample_rate, opts', [
     (FilterbankProcessor, 8000, dict(num_bins=40)),           # telephone speech: 200 samples -> 256
