@@ -840,6 +840,11 @@ int snf_debug_pitch_scratch(snf_plan* plan, void** down, void** nccf_res, void**
    filter's output on a RASTA plan, the input otherwise.  SNF_E_INVALID for a plan of another kind. */
 int snf_debug_plp_tail(snf_plan* plan, const float* mel, const double* energy,
                        const int64_t* frame_offsets, int64_t n_utts, float* out, float* mel_out);
+/* Test aid: 1 when a batch with these host offset tables (`sample_offsets`, `frame_offsets`: int64
+   [n_utts + 1]) runs the 25 ms form of fbank512b_kernel with sample offsets relative to the first frame of
+   every frame set (32 bits per lane), 0 when it keeps 64-bit addresses: three consecutive utterances that
+   span 2^30 samples or more, or SNF_FBANK512B_ADDR64=1 in the environment.  Negative: an error code. */
+int snf_debug_fbank512b_rel32(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts);
 /* Duration in milliseconds of the kernels launched by the last run call on this plan, measured
    with HIP events on the stream the kernels were launched on.  `which` selects a kernel slot:
    0 = whole call, 1.. = per-kernel; returns <0 if the slot was not recorded. */

@@ -106,6 +106,7 @@ struct MelRoute {
   bool pairs = false;        // frame pair table (cached with the offsets unless the batch masks utterances out)
   bool frame_start = false;  // frame -> first sample / edge mark / utterance (cached with the offsets)
   bool noise_keys = false;   // dither: per-frame noise keys of fbank512b_kernel
+  bool rel32 = false;        // fbank512b_kernel: frame starts close enough for set-relative 32-bit sample offsets
   bool is_fast() const { return fe == FrontEnd::fast512 || fe == FrontEnd::dual256 || fe == FrontEnd::dual256_split; }
   bool is_dual() const { return fe == FrontEnd::dual256 || fe == FrontEnd::dual256_split; }
 };
@@ -157,6 +158,11 @@ MelRoute route_mel_batch(const snf_plan& plan, const int64_t* sample_offsets, co
   // choose that kernel for one of the plan's parameter sets
   r.noise_keys = plan.mp.dither != 0.0f && r.fe == FrontEnd::fast512 &&
                  (fbank512b_shape_ok(plan.fp, r.blocks) || (plan.wide && fbank512b_shape_ok(plan.fp_hi, r.blocks)));
+  // ... and addresses the samples relative to the first frame of a set where the batch's offsets allow it; a batch
+  // with three consecutive utterances that span 2^30 samples keeps the 64-bit form
+  // (the answer for the tables is kept with the host's copy of them: a pass over both for every call otherwise)
+  r.rel32 = r.fe == FrontEnd::fast512 && !r.blocks && !fbank512b_addr64_knob() &&
+            (plan.oc.rel32 >= 0 ? plan.oc.rel32 == 1 : fbank512b_rel32_spans_ok(sample_offsets, frame_offsets, n_utts));
   return r;
 }
 
@@ -399,6 +405,9 @@ int snf_plan_run_batch_device(snf_plan* plan, const int16_t* d_wave, const int64
   const MelRoute r = route_mel_batch(*plan, sample_offsets, frame_offsets, n_utts, any_warp);
   if (r.fused && (!r.is_fast() || r.any_short))
     return set_error(SNF_E_RUNTIME, "append_deltas: this batch cannot run on the 512-point path");
+  if (r.rel32) b.rel32_samples = sample_offsets[n_utts];
+  if (r.fe == FrontEnd::fast512 && !r.blocks && !fbank512b_addr64_knob() && !oc.h_foff.empty())
+    oc.rel32 = r.rel32 ? 1 : 0;  // (the tables are the cached ones: kept for the calls that bring them again)
   MelCall c{plan, r, s, own_stream, b, b};
   if ((rc = prepare_mel_tables(&c, sample_offsets, frame_offsets, warp_ids))) return rc;
 
@@ -544,6 +553,13 @@ int snf_debug_plp_tail(snf_plan* plan, const float* mel, const double* energy, c
   // (also after a refusal: the uploads read the caller's arrays, and the buffers are freed on return)
   SNF_HIP_CHECK(hipStreamSynchronize(s));
   return rc;
+}
+
+// Test aid (include/shennong_amd.h): the route's decision between the two sample addressings of fbank512b_kernel,
+// from host offset tables alone (no plan, no device).
+int snf_debug_fbank512b_rel32(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts) {
+  if (!sample_offsets || !frame_offsets || n_utts < 0) return set_error(SNF_E_INVALID, "null offsets table");
+  return fbank512b_rel32_ok(sample_offsets, frame_offsets, n_utts) ? 1 : 0;
 }
 
 }  // extern "C"

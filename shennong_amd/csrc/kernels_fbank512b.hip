@@ -31,6 +31,7 @@
 #include <float.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "snf_internal.h"
 #include "device_fft.h"
@@ -40,6 +41,7 @@ namespace snf {
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // the LDS layout of the family (snf_internal.h: same table blob, same tiles) under the names the kernel body uses
 constexpr int kWaves = kFast512MaxWaves;          // one 16-wave workgroup per CU (4 waves per SIMD)
@@ -84,7 +86,18 @@ constexpr int kTileBytes = kFast512TileBytes;     // wave-private LDS per frame
 // instruction and no wait between them.  The MFCC tail requests its six constant DCT rows in front of the logs and
 // the log-mel write and keeps the lifter of the lane in a register.  Every other plan, the NJ = 16 forms and the
 // few NJ = 13 forms that have no registers for it (launch_plan) run the code of before (MMQ = 0).
-template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV>
+// Set addressing off the vector pipe (REL, NJ = 13; profiles/NOTEBOOK.md 4.1f, profiles/fbank512b_addr_*).  The clamp of
+// the frame index, &frame_start[...], the sample pointer of the lane and the select of element 12's address were
+// 64-bit vector arithmetic per lane and set (v_lshl_add_u64, 64-bit compares - the scalar unit has no ordered one -
+// v_cndmask pairs: all half rate), yet only the 64-bit start of the lane's frame differs between lanes by more than
+// a constant.  With REL the table reads go through a buffer over the rows of the set (scalar base
+// &frame_start[set * 4], lane constant 8 q; the buffer's bound stands in for the clamp) and the samples come
+// through a buffer whose base is the first sample of the set's row 0 (v_readfirstlane, as `wid`) and which ends
+// with the batch: one 32-bit offset per lane and set, the thirteen loads carry 64 j as immediates; frame and set
+// indices are 32-bit.  The host (fbank512b_rel32_ok) sets BatchArgs::rel32_samples only where the starts of any
+// four consecutive frames lie less than 2^30 samples apart and the batch has fewer than 2^30 frames; every other
+// batch, and the NJ = 16 forms, run the addressing of before (REL = false).
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV, bool REL>
 __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512Params p, const BatchArgs b,
                                                                   float* __restrict__ out,
                                                                   double* __restrict__ energy_out) {
@@ -137,10 +150,14 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
   if (NJ == 13 && KIND == SNF_KIND_MFCC) lifter_once = t_lifter[l];
 
   const float win_len_f = static_cast<float>(p.win_len), inv_win_len = 1.0f / win_len_f;
-  const int64_t n_sets = (b.total_frames + 3) >> 2;
-  const int64_t set_stride = static_cast<int64_t>(gridDim.x) * kWaves;
-  const int64_t last_frame = b.total_frames - 1;
-  int64_t set = static_cast<int64_t>(blockIdx.x) * kWaves + wid;
+  // (REL: frame and set indices are 32-bit integers - fbank512b_rel32_ok admits batches below 2^30 frames - so
+  // that the tests on them are scalar compares; the scalar unit has no ordered 64-bit compare)
+  using idx_t = typename std::conditional<REL, int, int64_t>::type;
+  const idx_t total_frames = static_cast<idx_t>(b.total_frames);
+  const idx_t n_sets = (total_frames + 3) >> 2;
+  const idx_t set_stride = static_cast<idx_t>(gridDim.x) * kWaves;
+  const idx_t last_frame = total_frames - 1;
+  idx_t set = static_cast<idx_t>(blockIdx.x) * kWaves + wid;
   if (set >= n_sets) return;
 
   // NJ = 13: the 25 ms / 16 kHz window (only element j = 12 can fall outside it); NJ = 16: any other
@@ -150,19 +167,62 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     if (NJ == 13) return j < NJ - 1 || in_last;
     return 2 * (l + 16 * j) < p.win_len;
   };
-  auto start_of = [&](int64_t s) -> int64_t {  // first sample of the lane's frame of set s (clamped)
+  static_assert(!REL || NJ == 13, "set-relative addressing: the 25 ms forms");
+  // REL: the rows of set s in a table of 8-byte entries as a buffer - the rows that are frames: four, fewer in the
+  // last set of the batch, none in the look-ahead past it.  A row outside it reads 0, where the form below reads
+  // the last frame again: its features are computed from whatever the sample buffer gives and never stored.
+  const unsigned q8 = static_cast<unsigned>(q) * 8u;
+  auto set_rows_of = [&](const void* table, idx_t s) -> uint64_t {
+    int rows = static_cast<int>(total_frames) - static_cast<int>(s) * 4;
+    rows = rows < 0 ? 0 : rows;
+    asm volatile("" : "+s"(rows));  // (two scalar instructions: as one clamp the compiler takes v_med3_i32)
+    rows = rows > 4 ? 4 : rows;
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<char*>(static_cast<const char*>(table)) + static_cast<int64_t>(s) * 32, 0, rows * 8, 0x00020000);
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rsrc, q8, 0, 0);
+    return (static_cast<uint64_t>(v.y) << 32) | v.x;
+  };
+  auto start_of = [&](idx_t s) -> int64_t {  // first sample of the lane's frame of set s (clamped)
+    if (REL) return static_cast<int64_t>(set_rows_of(b.frame_start, s));
     const int64_t gi = s * 4 + q;
     return b.frame_start[gi < last_frame ? gi : last_frame];
   };
-  auto noise_of = [&](int64_t s) -> unsigned long long {  // ... and its noise key
+  auto noise_of = [&](idx_t s) -> unsigned long long {  // ... and its noise key
+    if (!DITHER) return 0ull;
+    if (REL) return set_rows_of(b.frame_noise, s);
     const int64_t gi = s * 4 + q;
-    return DITHER ? b.frame_noise[gi < last_frame ? gi : last_frame] : 0ull;
+    return b.frame_noise[gi < last_frame ? gi : last_frame];
   };
   // Software pipeline over frame sets: one dword (two int16 samples) per element, requested a whole
   // iteration before it is converted; the start offset of the set after that arrives meanwhile.
   typedef int __attribute__((aligned(2))) int_a2;
   int raw[NJ];
+  // REL: element 12 of a lane outside the window re-reads the first dword of its frame, like the form below
+  const unsigned l4 = 4u * l, off12 = in_last ? l4 + 64u * 12u : 0u;
   auto request = [&](int64_t st) {
+    if (REL) {
+      // The samples of the set as a buffer: from the first sample of row 0 to the end of the batch.  Row 0 has the
+      // lowest start of the set (the starts rise with the frame index), so the other rows lie at unsigned 32-bit
+      // byte offsets from it (fbank512b_rel32_ok).  A row that is no frame (start 0, see above) gets whatever
+      // offset the subtraction wraps to: inside the buffer it reads samples of the batch, outside it reads 0.
+      const unsigned lo = static_cast<unsigned>(st), hi = static_cast<unsigned>(static_cast<uint64_t>(st) >> 32);
+      const unsigned lo0 = __builtin_amdgcn_readfirstlane(lo), hi0 = __builtin_amdgcn_readfirstlane(hi);
+      const int64_t st0 = static_cast<int64_t>((static_cast<uint64_t>(hi0) << 32) | lo0);
+      const int64_t left = b.rel32_samples - st0;  // samples from there to the end of the batch (scalar)
+      unsigned over = static_cast<unsigned>(static_cast<uint64_t>(left) >> 31);
+      asm volatile("" : "+s"(over));  // (a test of the upper bits in the scalar unit, not a 64-bit vector compare)
+      const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<int16_t*>(b.wave + st0), 0, over != 0u ? -1 : static_cast<int>(static_cast<unsigned>(left) << 1),
+          0x00020000);
+      unsigned off = ((lo - lo0) << 1) + l4, last = ((lo - lo0) << 1) + off12;
+      // (finished values: the thirteen loads carry 64 j as immediates instead of thirteen offsets of their own)
+      asm volatile("" : "+v"(off), "+v"(last));
+#pragma unroll
+      for (int j = 0; j < NJ - 1; ++j)
+        raw[j] = static_cast<int>(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, off + 64u * j, 0, 0));
+      raw[NJ - 1] = static_cast<int>(__builtin_amdgcn_raw_buffer_load_b32(wrsrc, last, 0, 0));
+      return;
+    }
     const int16_t* __restrict__ wp = b.wave + st;
     const int16_t* __restrict__ wl = wp + 2 * l;
 #pragma unroll
@@ -186,7 +246,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
   }
 
   for (; set < n_sets; set += set_stride) {
-    const int64_t g = set * 4 + q;  // global frame = output row
+    const idx_t g = set * 4 + q;  // global frame = output row
     const bool valid = g <= last_frame;
 
     // ---- A: DC removal, pre-emphasis, window (Kaldi's ProcessWindow order) -------------------------
@@ -390,9 +450,9 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     }
     float* __restrict__ row = out + g * static_cast<int64_t>(p.out_cols);  // (stores of the non-BST forms)
     // the rows of this set as a buffer: rows past the last frame fall outside it (BST)
-    const int64_t rows_left = b.total_frames - set * 4;
+    const idx_t rows_left = total_frames - set * 4;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
-        out + set * 4 * static_cast<int64_t>(p.out_cols), 0,
+        out + static_cast<int64_t>(set) * 4 * static_cast<int64_t>(p.out_cols), 0,
         (rows_left < 4 ? static_cast<int>(rows_left) : 4) * p.out_cols * 4, 0x00020000);
     {
       // ---- F: mel filterbank on the matrix pipe (see fbank512_kernel) -------------------------------
@@ -497,7 +557,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
               mm_out >= 0 ? (mj * p.out_cols + mm_out) * 4 : -1, 0, 2);
         } else {
           if (mvalid && mm_out >= 0) {
-            float* __restrict__ dst = out + (set * 4 + mj) * static_cast<int64_t>(p.out_cols) + mel_col + mm_out;
+            float* __restrict__ dst = out + static_cast<int64_t>(set * 4 + mj) * p.out_cols + mel_col + mm_out;
             if (mm_out + 4 <= p.num_bins) {
               __builtin_nontemporal_store(f32x4_a4{mel[0], mel[1], mel[2], mel[3]}, reinterpret_cast<f32x4_a4*>(dst));
             } else {
@@ -607,6 +667,38 @@ bool fbank512b_shape_ok(const Fast512Params& p, bool per_utt) {
   if (p.kind != SNF_KIND_FBANK && p.kind != SNF_KIND_MFCC && p.kind != SNF_KIND_PLP) return false;
   return fast512_lds_bytes(p.table_floats, kWaves, false) <= kFast512LdsBytes;
 }
+// Set-relative 32-bit sample addressing (fbank512b_kernel, REL): the four frames of a set lie in at most four
+// consecutive utterances that have frames (and the frameless ones between them), so the distance from the first
+// sample of a set's first row to that of any other row is below the samples that three such utterances span, the
+// frameless ones behind each included.  Below 2^30 samples the byte offsets (twice that, plus the window) fit the
+// 32 bits of a buffer offset.  The kernel also counts frames in 32 bits there.  A function of the offset tables alone
+// (the host layer keeps the answer with its copy of the tables: OffsetsCache::rel32).
+bool fbank512b_rel32_spans_ok(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts) {
+  constexpr int64_t kLimit = int64_t{1} << 30;
+  if (frame_offsets[n_utts] >= kLimit) return false;  // (32-bit frame and set indices, look-ahead included)
+  int64_t first[3];  // first samples of the last (up to) three utterances with frames, oldest first
+  int held = 0;
+  for (int64_t u = 0; u < n_utts; ++u) {
+    if (frame_offsets[u + 1] == frame_offsets[u]) continue;
+    if (held == 3) {  // the span of the oldest ends where this utterance begins
+      if (sample_offsets[u] - first[0] >= kLimit) return false;
+      first[0] = first[1];
+      first[1] = first[2];
+      --held;
+    }
+    first[held++] = sample_offsets[u];
+  }
+  // (the end of the batch closes the spans that are still open: the oldest is the longest)
+  return held == 0 || sample_offsets[n_utts] - first[0] < kLimit;
+}
+// SNF_FBANK512B_ADDR64=1 keeps every batch on the 64-bit form (A/B runs; read at every call, like SNF_FBANK512_OLD)
+bool fbank512b_addr64_knob() {
+  const char* knob = getenv("SNF_FBANK512B_ADDR64");
+  return knob && knob[0] == '1';
+}
+bool fbank512b_rel32_ok(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts) {
+  return !fbank512b_addr64_knob() && fbank512b_rel32_spans_ok(sample_offsets, frame_offsets, n_utts);
+}
 bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b) {
   if (p.dither != 0.0f && b.frame_noise == nullptr) return false;  // (no key table: fbank512_kernel draws its own)
   return fbank512b_shape_ok(p, b.blk_utt != nullptr);
@@ -614,13 +706,13 @@ bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b) {
 
 namespace {
 
-template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV>
-int launch_dither(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV, bool REL>
+int launch_form(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
   const size_t lds = fast512_lds_bytes(q.table_floats, kWaves, false);
   const int64_t n_sets = (b.total_frames + 3) / 4;
   int64_t blocks = (n_sets + kWaves - 1) / kWaves;
   if (blocks > 256) blocks = 256;  // one resident workgroup per CU, grid-stride over the frame sets
-  auto kern = fbank512b_kernel<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV>;
+  auto kern = fbank512b_kernel<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, REL>;
   if (lds > 64 * 1024)
     SNF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
@@ -628,6 +720,18 @@ int launch_dither(const Fast512Params& q, const BatchArgs& b, float* out, double
                      energy_out);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
+}
+
+// Set-relative sample addressing (REL) where the host found the batch's frame starts close enough
+// (BatchArgs::rel32_samples, fbank512b_rel32_ok); the 20 / 30 ms forms keep the 64-bit addressing.
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV>
+int launch_dither(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
+  // (MFCC with dither on the 7-quad, 3-block plan: spills 2-4 registers with it, none without)
+  if constexpr (NJ == 13 && !(KIND == SNF_KIND_MFCC && DITHER && MMQ == 7 && LV == 3)) {
+    if (b.rel32_samples > 0)
+      return launch_form<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, true>(q, b, out, energy_out, stream);
+  }
+  return launch_form<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, false>(q, b, out, energy_out, stream);
 }
 
 // The mel plan as a compile-time property of the launch (NJ = 13): chain length 7 / 6 quads and 2-3 / 4 blocks per

@@ -139,6 +139,7 @@ struct OffsetsCache {
   bool pairs_valid = false;   // ... the frame pair table (n_pairs records)
   int64_t n_pairs = 0;
   int tile_cols = -1;         // ... the delta kernel's tile records, built for rows of this width (-1: none)
+  int rel32 = -1;             // fbank512b_rel32_spans_ok of the cached tables (-1: not asked yet)
 
   // (post-processor plans have no sample offsets: null)
   bool same(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts) const {
@@ -153,6 +154,7 @@ struct OffsetsCache {
     h_foff.clear();
     setidx_valid = pairs_valid = false;
     tile_cols = -1;
+    rel32 = -1;
   }
   int store(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts, hipStream_t s) {
     invalidate();

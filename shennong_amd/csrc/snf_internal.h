@@ -149,6 +149,9 @@ struct BatchArgs {
   int64_t n_blocks;
   int64_t n_utts;
   int64_t total_frames;
+  // fbank512b_kernel: the samples of the whole batch where the set-relative 32-bit sample addressing holds for it
+  // (fbank512b_rel32_ok, decided by route_mel_batch), 0 where the kernel keeps 64-bit addresses per lane
+  int64_t rel32_samples;
 };
 
 // The noise stream of a frame (dither, delta-pitch noise) is keyed by what the frame IS, not by where it
@@ -293,6 +296,12 @@ int launch_build_utt_noise(const BatchArgs& b, uint32_t* d_words, hipStream_t st
 bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b);
 // ... everything of it that does not depend on the frames' noise key table: whoever makes that table asks this
 bool fbank512b_shape_ok(const Fast512Params& p, bool per_utt);
+// ... and whether the frame starts of any four consecutive frames of the batch lie less than 2^30 samples apart
+// (host offset tables): the kernel's set-relative 32-bit sample addressing
+bool fbank512b_rel32_spans_ok(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts);
+// ... unless SNF_FBANK512B_ADDR64=1 keeps every batch on the 64-bit form (read at every call)
+bool fbank512b_addr64_knob();
+bool fbank512b_rel32_ok(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts);
 int launch_fbank512b(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
                      double* energy_out, hipStream_t stream);
 
