@@ -731,6 +731,33 @@ int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t
                   const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
                   int32_t metric, float* d_cost, int32_t* d_len, void* stream);
 
+/* ---- ABX triplet counts over a table of distances (the two steps after the distances in the reference's examples) --
+ * An extension with no reference call behind it: the reference's examples run `abx-score` and `abx-analyze` of an
+ * external toolkit on the CPU (reference examples/features_abx/scripts/abx_score.sh:22-23), one triplet at a time,
+ * and average the scores of the cells (examples/features_abx/scripts/collapse_abx.py:35-42).  Here the triplets of
+ * all the cells of a call are counted on the device from distances that lie in HBM, as snf_dtw_pairs leaves them;
+ * the scores and their collapse are host arithmetic on the counts (shennong_amd/abx.py).  The definitions are this
+ * project's own (tests/abx_np.py); agreement with that toolkit is unpinned.
+ *
+ * Cell c is the record h_cells[8 c ..] = {offA, offB, stride, nA, nB, nX, same, 0}.  With v[i] = d_cost[i] /
+ * (float)d_len[i] (the correctly rounded float32 division: the value of dtw_distances(normalized=True) bit for
+ * bit), or v[i] = d_cost[i] when d_len is NULL, its triplets are (a, b, x) in [0, nA) x [0, nB) x [0, nX), without
+ * those with a == x when same != 0 (the A-list and the X-list are then the same items), and
+ *   dAX = v[offA + x stride + a], dBX = v[offB + x stride + b]
+ *   d_counts[3 c]     = less  = #{dAX < dBX}
+ *   d_counts[3 c + 1] = equal = #{dAX == dBX}
+ *   d_counts[3 c + 2] = bad   = #{dAX or dBX not finite}; a bad triplet is in neither of the other two counts.
+ * The counts are exact integers and do not depend on how the device splits the work; every element of d_counts is
+ * written; non-finite distances change counts and nothing else.  SNF_E_INVALID, before any device work: a null or
+ * misaligned pointer, a negative size, nA, nB or nX below 1 (or 2^31 and above), a negative offset or stride, a
+ * cell whose last element reaches outside [0, n_dist), same != 0 with nA != nX, a nonzero last word, a cell of
+ * more than 2^62 triplets.  n_cells = 0 does nothing.  The cell table is a HOST array that the call uploads.
+ * Everything is enqueued on `stream` and the call returns without waiting for it (the tables are kept in a slot of
+ * their own until the kernels have run); `stream` NULL: the calling thread's own stream, which the call waits for
+ * before returning. */
+int snf_abx_cells(int device_id, const float* d_cost, const int32_t* d_len, int64_t n_dist, const int64_t* h_cells,
+                  int64_t n_cells, uint64_t* d_counts, void* stream);
+
 /* ---- device memory + timing (so hosts without torch can keep data resident in HBM) ---------- */
 int snf_malloc(void** dptr, uint64_t bytes);
 int snf_free(void* dptr);

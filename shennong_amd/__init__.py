@@ -5,6 +5,7 @@ Features``, ``process_all``, ``get_params/set_params``) with the arithmetic in h
 kernels behind the C ABI of ``include/shennong_amd.h``.  See README.md / DESIGN.md.
 """
 
+from shennong_amd.abx import abx_scores
 from shennong_amd.audio import Audio
 from shennong_amd.dtw import dtw_distances
 from shennong_amd.features import Features, FeaturesCollection
@@ -12,4 +13,5 @@ from shennong_amd.utterances import Utterance, Utterances
 
 __version__ = '0.1.0'
 
-__all__ = ['Audio', 'Features', 'FeaturesCollection', 'Utterance', 'Utterances', 'dtw_distances']
+__all__ = ['Audio', 'Features', 'FeaturesCollection', 'Utterance', 'Utterances', 'abx_scores',
+           'dtw_distances']

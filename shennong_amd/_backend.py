@@ -49,7 +49,7 @@ EXPORTS = [
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
     'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
     'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs',
-    'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs']
+    'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs', 'snf_abx_cells']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -205,6 +205,7 @@ def lib():
         L.snf_collate_num_out.restype = i64
         L.snf_collate_padded.argtypes = [i32, vp, i32, pi64, i64, i32, i32, i32, i32, i32, f32, i64, vp, vp, vp]
         L.snf_dtw_pairs.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, vp, vp, vp]
+        L.snf_abx_cells.argtypes = [i32, vp, vp, i64, pi64, i64, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
         L.snf_set_oom_hook(_OOM_HOOK)
@@ -1053,6 +1054,17 @@ def dtw_pairs(d_rows, dim, item_first, item_count, pairs, metric, d_cost, d_len,
         first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int32)), first.shape[0],
         pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], DTW_METRICS[metric], C.c_void_p(d_cost),
         C.c_void_p(d_len), C.c_void_p(stream) if stream else None))
+
+
+def abx_cells(d_cost, d_len, n_dist, cells, d_counts, device=None, stream=None):
+    """ABX triplet counts (uint64 [n_cells, 3] at `d_counts`: less, equal, bad) of the cell records `cells`
+    [n_cells, 8] over the `n_dist` distances at the device pointers `d_cost` (float32) and `d_len` (int32, or
+    None: the raw cost is compared): see snf_abx_cells in include/shennong_amd.h"""
+    cells = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1, 8)
+    check(lib().snf_abx_cells(
+        _DEVICE if device is None else int(device), C.c_void_p(d_cost), C.c_void_p(d_len) if d_len else None,
+        int(n_dist), cells.ctypes.data_as(C.POINTER(C.c_int64)), cells.shape[0], C.c_void_p(d_counts),
+        C.c_void_p(stream) if stream else None))
 
 
 def check_finite_device(d_ptr, count, device=None):

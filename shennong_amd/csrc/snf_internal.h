@@ -420,6 +420,23 @@ int launch_dtw_pairs(const float* rows, int dim, const DtwItem* d_items, const D
                      const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
                      int compute_units, float* cost, int32_t* len, hipStream_t stream);
 
+// kernels_abx.hip: ABX triplet counts per cell over a table of distances (snf_abx_cells)
+constexpr int kAbxTile = 1024;        // floats of a B-row staged in LDS at a time (4 KB per wave)
+struct AbxCell {
+  int64_t offA, offB, stride;   // dAX = element offA + x stride + a, dBX = element offB + x stride + b
+  int32_t nA, nB, nX, same;     // every one of nA, nB, nX in [1, 2^31): the host has checked
+};
+struct AbxUnit {
+  int32_t cell;       // index into the cell table (the caller's order: where the counts go)
+  int32_t x0, x1;     // the stretch of X this unit counts
+  int32_t split;      // 1: the cell has other units, the counts are added with 64-bit vector atomics
+};
+// `d_small`: the cells that one lane counts each; `d_units`: whole cells and stretches of split cells, one wave
+// each, sorted by work descending.  `d_counts` [n_cells][3] has been zeroed in stream order when a unit is split.
+int launch_abx_cells(const float* cost, const int32_t* len, const AbxCell* d_cells, const int32_t* d_small,
+                     int64_t n_small, const AbxUnit* d_units, int64_t n_units, int compute_units,
+                     unsigned long long* d_counts, hipStream_t stream);
+
 struct PitchPostParams {
   snf_pitch_post_options o;
   int ndims;
