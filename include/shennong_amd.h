@@ -380,6 +380,15 @@ int snf_gmm_selection_posteriors(int device_id, const float* d_x, int64_t n_fram
                                  const float* d_gconsts, const float* d_means_invvars, const float* d_inv_vars,
                                  int32_t num_gauss, const int32_t* d_gselect, int32_t num_gselect, float min_post,
                                  float* d_post, float* d_loglike, void* stream);
+/* Dense posteriors, the posteriorgram of the model (an extension: the reference hands out the pruned posteriors of a
+ * selection only): d_post[n_frames x num_gauss] float32 row-major, d_post[f, c] = expf(L[f, c] - lse_f) with
+ * lse_f the per-frame log-sum-exp over all Gaussians, the one snf_gmm_accumulate computes (bit-equal; written to
+ * d_lse[n_frames] unless that is NULL).  L is recomputed per 64-frame tile as in the E-step: no
+ * [n_frames x num_gauss] block of L goes through memory.  Every element of d_post is written.  The rows are what
+ * snf_dtw_pairs' SNF_DTW_SYMKL compares. */
+int snf_gmm_posteriors(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                       const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss, float* d_post,
+                       float* d_lse, void* stream);
 
 /* ---- linear VTLN (reference processor/vtln.py, VtlnProcessor) ----------------------------------
  * Segments: contiguous runs of frames, h_seg_offsets[n_segments + 1] (HOST int64, non-decreasing, first 0,
@@ -711,6 +720,13 @@ int snf_collate_padded(int device_id, const float* d_in, int32_t dim, const int6
  */
 #define SNF_DTW_COSINE 0       /* acos(clamp(cos(x_i, y_j), -1, 1)) / pi; 1 if one row is zero, 0 if both */
 #define SNF_DTW_SQEUCLIDEAN 1  /* sum_k (x_ik - y_jk)^2, as max(|x_i|^2 + |y_j|^2 - 2 x_i . y_j, 0)      */
+/* Symmetric KL divergence of rows of probabilities (posteriorgrams: snf_gmm_posteriors), natural logarithm:
+ * 0.5 sum_k (x~_ik - y~_jk) (ln x~_ik - ln y~_jk) with x~ = max(x, SNF_DTW_SYMKL_FLOOR) element-wise (zero and
+ * negative entries count as the floor; rows need not sum to 1), computed as
+ * max(0.5 (h(x_i) + h(y_j) - x~_i . ln y~_j - ln x~_i . y~_j), 0), h(r) = sum_k r~_k ln r~_k (DESIGN 4.16,
+ * tests/symkl_f64.py).  This project's own definition too: agreement with the ABX toolkit's KL is unpinned. */
+#define SNF_DTW_SYMKL 2
+#define SNF_DTW_SYMKL_FLOOR 0x1p-40f /* 2^-40, exact in float32 */
 #define SNF_DTW_MAX_FRAMES 4096 /* rows of one item */
 #define SNF_DTW_MAX_DIM 4096
 /* Item t is the rows [h_item_first[t], h_item_first[t] + h_item_count[t]) of the float32 block d_rows [., dim];
@@ -726,7 +742,9 @@ int snf_collate_padded(int device_id, const float* d_in, int32_t dim, const int6
  * [0, n_items), an unknown metric, a null or misaligned pointer.  n_pairs = 0 does nothing.  The tables are HOST
  * arrays that the call uploads.  Everything is enqueued on `stream` and the call returns without waiting for it
  * (the tables and the row norms are kept in a slot of their own until the kernels have run); `stream` NULL: the
- * calling thread's own stream, which the call waits for before returning. */
+ * calling thread's own stream, which the call waits for before returning.  SNF_DTW_SYMKL keeps, in that slot, the
+ * logarithms of every row between the first and the last row of the items too: (dim + 1) floats per row; when
+ * that cannot be allocated the call fails with SNF_E_HIP before any kernel is launched. */
 int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
                   const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
                   int32_t metric, float* d_cost, int32_t* d_len, void* stream);

@@ -42,7 +42,7 @@ EXPORTS = [
     'snf_event_create', 'snf_event_destroy', 'snf_event_record', 'snf_event_elapsed_ms', 'snf_mem_info',
     'snf_stream_wait_event', 'snf_stream_query', 'snf_event_synchronize', 'snf_wav_scan', 'snf_wav_read_pcm16',
     'snf_gmm_loglikes', 'snf_gmm_accumulate', 'snf_gmm_gselect', 'snf_gmm_gselect_preselect',
-    'snf_gmm_selection_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
+    'snf_gmm_selection_posteriors', 'snf_gmm_posteriors', 'snf_fmllr_accumulate', 'snf_vtln_gram', 'snf_lvtln_select',
     'snf_affine_apply_segments', 'snf_vtln_gram_rows', 'snf_dense_layer', 'snf_bottleneck_vad',
     'snf_bottleneck_fbank', 'snf_bottleneck_nn_input', 'snf_bottleneck_forward', 'snf_crepe_conv',
     'snf_crepe_forward', 'snf_crepe_decode', 'snf_framed_onehot', 'snf_packed_weights_bf16_size',
@@ -168,6 +168,7 @@ def lib():
         L.snf_gmm_gselect.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, i32, vp, vp, vp]
         L.snf_gmm_gselect_preselect.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp]
         L.snf_gmm_selection_posteriors.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
+        L.snf_gmm_posteriors.argtypes = [i32, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp]
         L.snf_fmllr_accumulate.argtypes = [i32, vp, i64, i32, vp, vp, i32, vp, vp, i32, vp, i64, vp, vp]
         L.snf_vtln_gram.argtypes = [i32, vp, vp, vp, i64, i32, vp, vp]
         L.snf_vtln_gram_rows.argtypes = [i32, vp, vp, vp, vp, vp, i64, i32, vp, vp]
@@ -1036,7 +1037,7 @@ def collate_padded(d_in, dim, foff, dtype, left, right, subsample, offset, pad_v
         C.c_void_p(stream) if stream else None))
 
 
-DTW_METRICS = {'cosine': 0, 'sqeuclidean': 1}   # snf_dtw_pairs' metric
+DTW_METRICS = {'cosine': 0, 'sqeuclidean': 1, 'symkl': 2}   # snf_dtw_pairs' metric (SNF_DTW_*)
 DTW_MAX_FRAMES = 4096                            # SNF_DTW_MAX_FRAMES
 
 

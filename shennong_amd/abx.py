@@ -386,8 +386,9 @@ def abx_scores(features, items, on, across=None, by=(), metric='cosine', normali
     """The :class:`AbxTable` of the task (`on`, `across`, `by`) over `items` (an :class:`AbxItems`)
 
     `features`: a :class:`DeviceFeaturesCollection` (the rows are used where they lie), or a host
-    :class:`FeaturesCollection`, uploaded once.  `metric`, `normalized`: as in ``dtw_distances``; the normalised
-    value compared is the float32 quotient that ``dtw_distances(normalized=True)`` returns, bit for bit.
+    :class:`FeaturesCollection`, uploaded once.  `metric` ('cosine', 'sqeuclidean', or 'symkl' for posteriorgrams),
+    `normalized`: as in ``dtw_distances``; the normalised value compared is the float32 quotient that
+    ``dtw_distances(normalized=True)`` returns, bit for bit.
     The work is done in runs of whole by-blocks whose dense distance tables hold at most `max_pairs` pairs
     together; the distances never come to the host and the distances, path lengths and counts of a run are freed
     after it (the pair and cell tables of the last call stay in the slots of ``snf_dtw_pairs`` and

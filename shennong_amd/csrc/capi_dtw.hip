@@ -55,8 +55,8 @@ int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t
                   int32_t metric, float* d_cost, int32_t* d_len, void* stream) {
   if (dim < 1 || dim > kDtwMaxDim)
     return set_error(SNF_E_INVALID, "dtw: dim must be in [1, " + std::to_string(kDtwMaxDim) + "]");
-  if (metric != SNF_DTW_COSINE && metric != SNF_DTW_SQEUCLIDEAN)
-    return set_error(SNF_E_INVALID, "dtw: metric must be 0 (cosine) or 1 (sqeuclidean)");
+  if (metric != SNF_DTW_COSINE && metric != SNF_DTW_SQEUCLIDEAN && metric != SNF_DTW_SYMKL)
+    return set_error(SNF_E_INVALID, "dtw: metric must be 0 (cosine), 1 (sqeuclidean) or 2 (symkl)");
   if (n_items < 1 || n_items > 0x7fffffff) return set_error(SNF_E_INVALID, "dtw: number of items out of range");
   if (n_pairs < 0 || n_pairs > 0x7fffffff) return set_error(SNF_E_INVALID, "dtw: number of pairs out of range");
   if (!h_item_first || !h_item_count) return set_error(SNF_E_INVALID, "dtw: null item table");
@@ -141,7 +141,8 @@ int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t
   // (DevBuf::upload waits for the copy on the thread's own stream: the tables are pageable vectors that go away)
   int rc = slot->items.upload(items, mine->stream);
   if (!rc) rc = slot->pairs.upload(pairs, mine->stream);
-  if (!rc) rc = slot->aux.ensure(sizeof(float) * static_cast<size_t>(row_hi - row_lo));
+  // (symkl: the log block of the row range too; a failed allocation ends the call before any kernel)
+  if (!rc) rc = slot->aux.ensure(sizeof(float) * dtw_aux_floats(row_hi - row_lo, dim, metric));
   if (!rc)
     rc = launch_dtw_pairs(d_rows, dim, slot->items.as<DtwItem>(), slot->pairs.as<DtwPair>(), class_count, row_lo,
                           row_hi, slot->aux.as<float>(), metric, compute_units, d_cost, d_len, s);

@@ -128,6 +128,25 @@ int snf_gmm_selection_posteriors(int device_id, const float* d_x, int64_t n_fram
                     "gmm: selected Gaussian index out of range");
 }
 
+int snf_gmm_posteriors(int device_id, const float* d_x, int64_t n_frames, int32_t dim, const float* d_gconsts,
+                       const float* d_means_invvars, const float* d_inv_vars, int32_t num_gauss, float* d_post,
+                       float* d_lse, void* stream) {
+  int rc = gmm_check_model(n_frames, dim, num_gauss, d_x, d_gconsts, d_means_invvars, d_inv_vars);
+  if (rc) return rc;
+  if (n_frames > 0 && !d_post) return set_error(SNF_E_INVALID, "gmm: null output buffer");
+  if ((reinterpret_cast<uintptr_t>(d_post) & 3) || (reinterpret_cast<uintptr_t>(d_lse) & 3))
+    return set_error(SNF_E_INVALID, "gmm: output buffer not aligned to float32");
+  if (n_frames > (int64_t(1) << 40) / num_gauss) return set_error(SNF_E_INVALID, "gmm: posterior block too large");
+  if (n_frames == 0) return SNF_OK;
+  Planless lay;
+  auto tl_part = lay.take<double>(gmm_tiles(n_frames));
+  auto own_lse = lay.take<float>(d_lse ? 0 : n_frames);
+  if ((rc = lay.begin(device_id, stream))) return rc;
+  rc = launch_gmm_posteriors(d_x, n_frames, dim, d_gconsts, d_means_invvars, d_inv_vars, num_gauss,
+                             d_lse ? d_lse : own_lse, tl_part, d_post, lay.s);
+  return lay.finish(rc, "gmm posteriors kernels failed");
+}
+
 // ---- linear VTLN (kernels_vtln.hip) -------------------------------------------------------------
 namespace {
 int vtln_check_segments(const int64_t* off, int64_t S, int64_t F) {

@@ -3,12 +3,16 @@
 //
 //   d[i][j]  cosine:      acos(clamp(x_i . y_j / (|x_i| |y_j|), -1, 1)) / pi; 1 if one of the rows is zero, 0 if both
 //            sqeuclidean: max(|x_i|^2 + |y_j|^2 - 2 x_i . y_j, 0)
+//            symkl:       max(0.5 (h(x_i) + h(y_j) - x~_i . ln y~_j - ln x~_i . y~_j), 0), r~ = max(r, 2^-40)
+//                         element-wise, h(r) = sum_k r~_k ln r~_k: 0.5 sum_k (x~ - y~)(ln x~ - ln y~)
 //   C[0][0] = d[0][0], L[0][0] = 1;   C[i][j] = d[i][j] + C[p], L[i][j] = L[p] + 1
 //   p = the predecessor of smallest C among (i-1, j-1), (i-1, j), (i, j-1), ties to the first of that order
 //   cost = C[N-1][M-1], len = L[N-1][M-1]
 //
 // Pre-pass (dtw_rows_kernel): one thread per row of the block writes 1 / |row| (0 for a zero row) or |row|^2, the
-// sum of squares being one fused chain over k ascending.
+// sum of squares being one fused chain over k ascending.  For symkl (dtw_log_rows_kernel, one thread per row too)
+// it writes D + 1 floats per row: h(row), the same kind of chain over r~_k logf(r~_k), and behind it the row's
+// ln r~_k, which the main kernel takes its second operands from.
 //
 // Main kernel (dtw_pairs_kernel): one wavefront (a workgroup of 64) owns a pair and walks the pairs of its class
 // with the stride of the grid; the host has sorted every class by N M descending, so the strided walk hands
@@ -17,6 +21,8 @@
 //     dot products of a tile are two v_mfma_f32_32x32x2_f32 chains over k (lane l supplies x[l & 31][k0 + (l >> 5)]
 //     and y[l & 31][k0 + (l >> 5)] straight from memory, zeros beyond an odd D; rows and columns beyond the item
 //     repeat its last one and are never read back).  The chain is bit for bit fmaf over k ascending from zero.
+//     symkl runs the k loop twice into the same accumulators: floored rows of x against log rows of y, then log
+//     rows of x against floored rows of y (the floor is an fmaxf on the raw load; the padded k stay zero in both).
 //   * The epilogue turns the accumulators (row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31) into distances
 //     and writes them to a ring of SLOTS tiles in LDS, row stride S = 32 SLOTS floats: a half-wave writes 32
 //     consecutive words of one row.  The norms of the strip's rows sit in LDS (a broadcast read), the column's
@@ -38,6 +44,10 @@ namespace snf {
 
 int dtw_class_of(int32_t columns) { return columns <= 32 ? 0 : columns <= 512 ? 1 : 2; }
 
+size_t dtw_aux_floats(int64_t n_rows, int dim, int metric) {
+  return static_cast<size_t>(n_rows) * (metric == SNF_DTW_SYMKL ? static_cast<size_t>(dim) + 1 : 1);
+}
+
 namespace {
 
 constexpr int kSeam[kDtwClasses] = {32, 512, kDtwMaxFrames};
@@ -54,6 +64,28 @@ __global__ __launch_bounds__(256) void dtw_rows_kernel(const float* __restrict__
   aux[r] = metric == SNF_DTW_COSINE ? (s > 0.0f ? 1.0f / sqrtf(s) : 0.0f) : s;
 }
 
+constexpr float kSymklFloor = SNF_DTW_SYMKL_FLOOR;
+
+// symkl: dim + 1 floats of aux per row, r~ = max(row, floor): aux[r (dim + 1)] = h(row) = sum_k r~_k ln r~_k (one
+// fused chain over k ascending, the accurate logf), and behind it the row's logarithms ln r~_k
+__global__ __launch_bounds__(256) void dtw_log_rows_kernel(const float* __restrict__ rows, const int dim,
+                                                           const int64_t row_lo, const int64_t n,
+                                                           float* __restrict__ aux) {
+  const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (r >= n) return;
+  const float* p = rows + (row_lo + r) * dim;
+  float* q = aux + r * (dim + 1);
+  float s = 0.0f;
+  for (int k = 0; k < dim; ++k) {
+    const float v = fmaxf(p[k], kSymklFloor);
+    const float l = logf(v);
+    q[1 + k] = l;
+    s = fmaf(v, l, s);
+  }
+  q[0] = s;
+}
+
+// `dot`: the dot product; for symkl the sum of the two, x~_i . ln y~_j + ln x~_i . y~_j, with xa = h(x_i), ya = h(y_j)
 template <int METRIC>
 __device__ __forceinline__ float frame_distance(float dot, float xa, float ya) {
   if constexpr (METRIC == SNF_DTW_COSINE) {
@@ -62,6 +94,8 @@ __device__ __forceinline__ float frame_distance(float dot, float xa, float ya) {
     const float d = acosf(c) * 0.31830988618379067f;
     const bool xz = xa == 0.0f, yz = ya == 0.0f;
     return (xz || yz) ? ((xz && yz) ? 0.0f : 1.0f) : d;
+  } else if constexpr (METRIC == SNF_DTW_SYMKL) {
+    return fmaxf(0.5f * (xa + ya - dot), 0.0f);
   } else {
     return fmaxf(fmaf(-2.0f, dot, xa + ya), 0.0f);
   }
@@ -74,27 +108,26 @@ __device__ __forceinline__ int from_lane_below(int v) {
   return __builtin_amdgcn_update_dpp(0, v, 0x13C, 0xf, 0xf, false);
 }
 
-// The distances of the strip's 64 rows (32 unless `two`) against the 32 columns of a tile, into the ring at column
-// offset `c_off`.  `x0`, `x1`, `yc`: this lane's operand rows (lattice rows l & 31 and 32 + (l & 31), column l & 31).
-// The k loop goes in groups of 4 MFMA steps (8 k) whose 12 operand loads are issued one group ahead, before the
-// MFMAs of the group in hand: one wait per group instead of one per step.
-template <int METRIC, int S>
-__device__ __forceinline__ void make_tile(const float* __restrict__ x0, const float* __restrict__ x1,
-                                          const float* __restrict__ yc, const int dim, const bool two, const int lh,
-                                          const int li, const int c_off, const float ya, const float* xa,
-                                          float* ring) {
-  f32x16 acc0, acc1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.0f;
+// symkl: one pass of the k loop of a tile into `acc0`, `acc1` (make_tile has the loop of the other metrics, which
+// this one follows): the dot products of this lane's operand rows `x0`, `x1` (lattice rows l & 31 and 32 + (l & 31))
+// and `yc` (column l & 31).  The k loop goes in groups of 4 MFMA steps (8 k) whose 12 operand loads are issued one
+// group ahead, before the MFMAs of the group in hand: one wait per group instead of one per step.  FLOOR_A, FLOOR_B:
+// the operand is max(load, floor).
+template <bool FLOOR_A, bool FLOOR_B>
+__device__ __forceinline__ void tile_chain(const float* __restrict__ x0, const float* __restrict__ x1,
+                                           const float* __restrict__ yc, const int dim, const bool two, const int lh,
+                                           f32x16& acc0, f32x16& acc1) {
   float a0[4], a1[4], b[4], na0[4], na1[4], nb[4];
   auto load = [&](int g, float* A0, float* A1, float* B) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const int k = 8 * g + 2 * s + lh;
       const bool ok = k < dim;
-      B[s] = ok ? yc[k] : 0.0f;
-      A0[s] = ok ? x0[k] : 0.0f;
-      A1[s] = (ok && two) ? x1[k] : 0.0f;
+      // (the padded k of an odd D stay zero in both operands)
+      const float vb = ok ? yc[k] : 0.0f, v0 = ok ? x0[k] : 0.0f, v1 = (ok && two) ? x1[k] : 0.0f;
+      B[s] = (FLOOR_B && ok) ? fmaxf(vb, kSymklFloor) : vb;
+      A0[s] = (FLOOR_A && ok) ? fmaxf(v0, kSymklFloor) : v0;
+      A1[s] = (FLOOR_A && ok && two) ? fmaxf(v1, kSymklFloor) : v1;
     }
   };
   const int groups = (dim + 7) >> 3;
@@ -114,6 +147,58 @@ __device__ __forceinline__ void make_tile(const float* __restrict__ x0, const fl
         a0[s] = na0[s];
         a1[s] = na1[s];
         b[s] = nb[s];
+      }
+    }
+  }
+}
+
+// The distances of the strip's 64 rows (32 unless `two`) against the 32 columns of a tile, into the ring at column
+// offset `c_off`.  `x0`, `x1`, `yc`: this lane's operand rows (lattice rows l & 31 and 32 + (l & 31), column l & 31);
+// `lx0`, `lx1`, `lyc` (symkl only): the logarithms of the same rows, from `aux`.
+template <int METRIC, int S>
+__device__ __forceinline__ void make_tile(const float* __restrict__ x0, const float* __restrict__ x1,
+                                          const float* __restrict__ yc, const float* __restrict__ lx0,
+                                          const float* __restrict__ lx1, const float* __restrict__ lyc, const int dim,
+                                          const bool two, const int lh, const int li, const int c_off, const float ya,
+                                          const float* xa, float* ring) {
+  f32x16 acc0, acc1;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.0f;
+  if constexpr (METRIC == SNF_DTW_SYMKL) {
+    tile_chain<true, false>(x0, x1, lyc, dim, two, lh, acc0, acc1);    // x~ . ln y~
+    tile_chain<false, true>(lx0, lx1, yc, dim, two, lh, acc0, acc1);   // ln x~ . y~
+  } else {
+    // (cosine and sqeuclidean keep the loop as it stood, not a tile_chain<false, false>: that way their instances
+    // compile to the very instructions they had before symkl came: DESIGN 4.16)
+    float a0[4], a1[4], b[4], na0[4], na1[4], nb[4];
+    auto load = [&](int g, float* A0, float* A1, float* B) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int k = 8 * g + 2 * s + lh;
+        const bool ok = k < dim;
+        B[s] = ok ? yc[k] : 0.0f;
+        A0[s] = ok ? x0[k] : 0.0f;
+        A1[s] = (ok && two) ? x1[k] : 0.0f;
+      }
+    };
+    const int groups = (dim + 7) >> 3;
+    load(0, a0, a1, b);
+    for (int g = 0; g < groups; ++g) {
+      if (g + 1 < groups) load(g + 1, na0, na1, nb);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        if (8 * g + 2 * s < dim) {   // (the same for the whole wave; an odd D: the last step's second k is zero)
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], b[s], acc0, 0, 0, 0);
+          if (two) acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], b[s], acc1, 0, 0, 0);
+        }
+      }
+      if (g + 1 < groups) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          a0[s] = na0[s];
+          a1[s] = na1[s];
+          b[s] = nb[s];
+        }
       }
     }
   }
@@ -149,18 +234,25 @@ __global__ __launch_bounds__(64) void dtw_pairs_kernel(const float* __restrict__
     const int N = ix.frames, M = iy.frames;   // (1 <= N <= kDtwMaxFrames, 1 <= M <= SEAM: the host has checked)
     const float* X = rows + ix.row0 * dim;
     const float* Y = rows + iy.row0 * dim;
-    const float* ax = aux + (ix.row0 - row_lo);
-    const float* ay = aux + (iy.row0 - row_lo);
+    // one float of aux per row; symkl: dim + 1, h(row) and behind it the row's logarithms (dtw_log_rows_kernel)
+    const int64_t as = METRIC == SNF_DTW_SYMKL ? dim + 1 : 1;
+    const float* ax = aux + (ix.row0 - row_lo) * as;
+    const float* ay = aux + (iy.row0 - row_lo) * as;
     float C = 0.0f;
     int L = 0;
     for (int s0 = 0; s0 < N; s0 += 64) {
       const int R = min(64, N - s0);
       const bool more = s0 + 64 < N;
       __syncthreads();   // (the last strip's reads of xa are done)
-      xa[lane] = ax[min(s0 + lane, N - 1)];
+      xa[lane] = ax[min(s0 + lane, N - 1) * as];
       __syncthreads();
       const float* x0 = X + static_cast<int64_t>(min(s0 + li, N - 1)) * dim;
       const float* x1 = X + static_cast<int64_t>(min(s0 + 32 + li, N - 1)) * dim;
+      const float *lx0 = nullptr, *lx1 = nullptr;
+      if constexpr (METRIC == SNF_DTW_SYMKL) {
+        lx0 = ax + 1 + min(s0 + li, N - 1) * as;
+        lx1 = ax + 1 + min(s0 + 32 + li, N - 1) * as;
+      }
       float dgC = inf;   // (C, L) of cell (i - 1, j - 1): what came from lane i - 1 one step earlier
       int dgL = 0;
       int pos = -lane;   // (t - lane) mod S once t >= lane
@@ -170,8 +262,10 @@ __global__ __launch_bounds__(64) void dtw_pairs_kernel(const float* __restrict__
         if ((t & 31) == 0 && t < M) {   // (the same for the whole wave)
           const int col = min(t + li, M - 1);
           const float* yc = Y + static_cast<int64_t>(col) * dim;
-          const float ya = ay[col];
-          make_tile<METRIC, S>(x0, x1, yc, dim, R > 32, lh, li, 32 * slot, ya, xa, ring);
+          const float ya = ay[col * as];
+          const float* lyc = nullptr;
+          if constexpr (METRIC == SNF_DTW_SYMKL) lyc = ay + 1 + col * as;
+          make_tile<METRIC, S>(x0, x1, yc, lx0, lx1, lyc, dim, R > 32, lh, li, 32 * slot, ya, xa, ring);
           slot = slot + 1 == SLOTS ? 0 : slot + 1;
           __syncthreads();
         }
@@ -247,12 +341,18 @@ int launch_dtw_pairs(const float* rows, int dim, const DtwItem* d_items, const D
                      int compute_units, float* cost, int32_t* len, hipStream_t stream) {
   const int64_t n_rows = row_hi - row_lo;
   if (n_rows <= 0) return SNF_OK;
-  hipLaunchKernelGGL(dtw_rows_kernel, dim3(static_cast<unsigned>((n_rows + 255) / 256)), dim3(256), 0, stream, rows,
-                     dim, row_lo, n_rows, metric, d_aux);
+  const dim3 grid(static_cast<unsigned>((n_rows + 255) / 256)), block(256);
+  if (metric == SNF_DTW_SYMKL)   // (dim + 1 floats per row: dtw_aux_floats)
+    hipLaunchKernelGGL(dtw_log_rows_kernel, grid, block, 0, stream, rows, dim, row_lo, n_rows, d_aux);
+  else
+    hipLaunchKernelGGL(dtw_rows_kernel, grid, block, 0, stream, rows, dim, row_lo, n_rows, metric, d_aux);
   SNF_HIP_CHECK(hipGetLastError());
   if (metric == SNF_DTW_COSINE)
     launch_metric<SNF_DTW_COSINE>(rows, dim, d_items, d_pairs, class_count, d_aux, row_lo, compute_units, cost, len,
                                   stream);
+  else if (metric == SNF_DTW_SYMKL)
+    launch_metric<SNF_DTW_SYMKL>(rows, dim, d_items, d_pairs, class_count, d_aux, row_lo, compute_units, cost, len,
+                                 stream);
   else
     launch_metric<SNF_DTW_SQEUCLIDEAN>(rows, dim, d_items, d_pairs, class_count, d_aux, row_lo, compute_units, cost,
                                        len, stream);

@@ -44,7 +44,13 @@
 // Selection posteriors: gathered L of the selected Gaussians (gmm_sel_loglike_kernel), then one thread per
 // frame: Kaldi's VectorBase::ApplySoftMax and the reference's sequential min_post loop (ubm.py:559-569).
 //
+// Dense posteriors (snf_gmm_posteriors, the posteriorgram): gmm_dense_kernel<kLse> as in the E-step (unit weights;
+// lse is bit-equal to accumulate's), then gmm_posteriors_kernel recomputes L per 64-frame tile and 64-Gaussian block,
+// as gmm_stats_kernel does, and writes exp(L - lse_f): the block of P goes through LDS so that a thread stores 4
+// consecutive Gaussians of a frame (16 bytes when C % 4 == 0 and the output is aligned).  No [F x C] L in HBM.
+//
 // Resource usage (hipcc -O3 gfx950, -Rpass-analysis=kernel-resource-usage; scratch 0 B in every kernel):
+//   gmm_posteriors_kernel       57 VGPRs + 16 AGPRs, LDS 52 224 B: 3 waves/SIMD (LDS-bound: 3 workgroups/CU)
 //   gmm_dense_kernel<loglikes>  50 VGPRs + 16 AGPRs, LDS 34 816 B: 4 waves/SIMD (LDS-bound: 4 workgroups/CU)
 //   gmm_dense_kernel<lse>       58 VGPRs + 16 AGPRs, LDS 34 944 B: 4 waves/SIMD
 //   gmm_stats_kernel           230 VGPRs + 192 AGPRs, LDS 52 224 B: 1 wave/SIMD (the 8 x 4 fp64 partials and
@@ -296,6 +302,56 @@ __global__ void __launch_bounds__(kThreads) gmm_stats_kernel(const GmmArgs g, co
   }
 }
 
+// Dense posteriors of one 64-frame tile: post[f, c] = exp(L[f, c] - lse[f]) over all C in 64-Gaussian blocks, L
+// recomputed by the same device path as in gmm_stats_kernel.  The accumulators hold one Gaussian per lane; a block of
+// P goes through LDS (frame-major) so that a thread stores 4 consecutive Gaussians of a frame: 16 bytes where the
+// rows are aligned (`vec`: C % 4 == 0 and post 16-byte aligned), 16 threads = 256 contiguous bytes of a row.
+__global__ void __launch_bounds__(kThreads) gmm_posteriors_kernel(const GmmArgs g, const float* __restrict__ lse,
+                                                                 float* __restrict__ post, const int vec) {
+  __shared__ float xs[kTileF * kLd];
+  __shared__ float ws[kBlockC * kLd];
+  __shared__ __attribute__((aligned(16))) float pt[kTileF * kLd];   // P: pt[frame * kLd + Gaussian of the block]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, h = lane >> 4;
+  const int64_t f0 = static_cast<int64_t>(blockIdx.x) * kTileF;
+  const int64_t fr = f0 + wave * 16 + 4 * h;   // this lane's 4 frames: fr + r
+  float ls[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ls[r] = fr + r < g.F ? lse[fr + r] : 0.0f;
+  for (int c0 = 0; c0 < g.C; c0 += kBlockC) {
+    f32x4 acc[4];
+    dense_block(g, f0, c0, xs, ws, acc);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int cl = 16 * t + i, c = c0 + cl;
+      const float gc = c < g.C ? g.gconst[c] : 0.0f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float p = 0.0f;
+        if (c < g.C && fr + r < g.F) p = expf(ll_finish(gc, acc[t][r]) - ls[r]);
+        pt[(wave * 16 + 4 * h + r) * kLd + cl] = p;
+      }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < kTileF * (kBlockC / 4); e += kThreads) {
+      const int fl = e / (kBlockC / 4), c4 = 4 * (e % (kBlockC / 4));
+      const int64_t f = f0 + fl;
+      const int c = c0 + c4;
+      if (f >= g.F || c >= g.C) continue;
+      const float* src = pt + fl * kLd + c4;
+      float* dst = post + f * g.C + c;
+      if (vec) {   // (C % 4 == 0: the four are inside the row)
+        *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(src);
+      } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (c + q < g.C) dst[q] = src[q];
+      }
+    }
+    // (the next dense_block starts with a barrier before anything writes pt again)
+  }
+}
+
 __global__ void __launch_bounds__(kThreads) gmm_reduce_kernel(const double* __restrict__ part, int64_t n,
                                                              int64_t chunks, double* __restrict__ out) {
   const int64_t e = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
@@ -462,6 +518,22 @@ int launch_gmm_accumulate(const float* x, int64_t F, int D, const float* weights
   hipLaunchKernelGGL(gmm_reduce_kernel, dim3(blocks(n, kThreads)), dim3(kThreads), 0, stream, part, n, chunks, stats);
   SNF_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(gmm_reduce_one_kernel, dim3(1), dim3(kThreads), 0, stream, tl_part, ntiles, tot_like);
+  SNF_HIP_CHECK(hipGetLastError());
+  return SNF_OK;
+}
+
+int launch_gmm_posteriors(const float* x, int64_t F, int D, const float* gconst, const float* mi, const float* iv,
+                          int C, float* lse, double* tl_part, float* post, hipStream_t stream) {
+  if (F <= 0) return SNF_OK;
+  const GmmArgs g = make_args(x, F, D, gconst, mi, iv, C);
+  const int64_t ntiles = gmm_tiles(F);
+  // the E-step's own reduction (unit weights): lse is bit-equal to snf_gmm_accumulate's
+  hipLaunchKernelGGL(gmm_dense_kernel<kModeLse>, dim3(static_cast<unsigned>(ntiles)), dim3(kThreads), 0, stream, g,
+                     lse, nullptr, tl_part);
+  SNF_HIP_CHECK(hipGetLastError());
+  const int vec = (C % 4 == 0) && (reinterpret_cast<uintptr_t>(post) & 15) == 0;
+  hipLaunchKernelGGL(gmm_posteriors_kernel, dim3(static_cast<unsigned>(ntiles)), dim3(kThreads), 0, stream, g, lse,
+                     post, vec);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
 }

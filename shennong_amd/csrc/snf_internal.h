@@ -414,8 +414,10 @@ struct DtwPair {
   int32_t cells;    // frames(x) frames(y): the sort key
 };
 int dtw_class_of(int32_t columns);
+// floats of `d_aux` for n_rows rows: one per row; symkl: dim + 1 per row (h of the row, then its logarithms)
+size_t dtw_aux_floats(int64_t n_rows, int dim, int metric);
 // `d_pairs`: the pairs of class 0, then 1, then 2 (`class_count` of each), each class sorted by cells descending;
-// `d_aux`: one float per row of [row_lo, row_hi), written by the pre-pass
+// `d_aux`: dtw_aux_floats(row_hi - row_lo, dim, metric) floats, written by the pre-pass
 int launch_dtw_pairs(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
                      const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
                      int compute_units, float* cost, int32_t* len, hipStream_t stream);
@@ -454,6 +456,9 @@ int launch_gmm_loglikes(const float* x, int64_t F, int D, const float* gconst, c
 int launch_gmm_accumulate(const float* x, int64_t F, int D, const float* weights, const float* gconst,
                           const float* mi, const float* iv, int C, float* lse, double* tl_part, double* part,
                           double* stats, double* tot_like, hipStream_t stream);
+// lse [F] (the E-step's reduction, unit weights; tl_part [gmm_tiles(F)] scratch) and post[f, c] = exp(L[f, c] - lse[f])
+int launch_gmm_posteriors(const float* x, int64_t F, int D, const float* gconst, const float* mi, const float* iv,
+                          int C, float* lse, double* tl_part, float* post, hipStream_t stream);
 int launch_gmm_topn(const float* L, const int32_t* map, int64_t rows, int P, int n, int32_t* out_idx, float* out_lse,
                     hipStream_t stream);
 int launch_gmm_sel_loglikes(const float* x, int64_t F, int D, const float* gconst, const float* mi, const float* iv,

@@ -15,12 +15,15 @@ For the items x [N, D] and y [M, D] of a pair, with d[i, j] the frame distance o
 
     cosine       d = arccos(clip(x_i.y_j / (|x_i| |y_j|), -1, 1)) / pi; 1 if one of the rows is zero, 0 if both
     sqeuclidean  d = sum_k (x_ik - y_jk)^2
+    symkl        d = 0.5 sum_k (x~_ik - y~_jk) (ln x~_ik - ln y~_jk), x~ = max(x, 2^-40) element-wise: the symmetric
+                 KL divergence of rows of probabilities (posteriorgrams, ``DiagUbmProcessor.posteriorgrams``); zero
+                 and negative entries count as 2^-40, rows need not sum to 1
     C[0, 0] = d[0, 0], L[0, 0] = 1;  C[i, j] = d[i, j] + C[p], L[i, j] = L[p] + 1, p the predecessor of smallest
     C among (i-1, j-1), (i-1, j), (i, j-1), ties to the first of that order
     distance = C[N-1, M-1] / L[N-1, M-1] if normalized else C[N-1, M-1]
 
-The definition is this project's own (tests/dtw_f64.py states it in float64); agreement with the external toolkit
-is not pinned.
+The definition is this project's own (tests/dtw_f64.py and tests/symkl_f64.py state it in float64); agreement with
+the external toolkit, its KL divergence included, is not pinned (DESIGN sections 4.14 and 4.16).
 """
 
 import numpy as np
@@ -125,7 +128,7 @@ def dtw_distances(features, pairs, items=None, metric='cosine', normalized=True,
     `items` None: every utterance is one item and `pairs` holds pairs of names.  Otherwise a sequence of
     ``(name, onset, offset)`` in seconds - an item is the run of rows whose centre time lies in
     [onset, offset] - and `pairs` is an integer array [P, 2] into it.
-    `metric`: 'cosine' or 'sqeuclidean'.  `normalized`: the cost divided by the length of the path (float32
+    `metric`: 'cosine', 'sqeuclidean' or 'symkl' (the module's docstring).  `normalized`: the cost divided by the length of the path (float32
     division on the host; the kernel writes both).  `return_lengths`: ``(distances, lengths)``, lengths int32.
 
     ValueError, before any device work: an unknown metric, a name that is not in the collection, an index out of

@@ -392,6 +392,22 @@ class FrameBlock:
             None))
         return out.download(np.empty((self.nframes, dgmm.num_gauss), dtype=np.float32))
 
+    def posteriors(self, dgmm, out=None, with_lse=False):
+        """Dense posteriors ``exp(L - lse)`` [F, C] float32 (snf_gmm_posteriors).  `out` None: a host array.
+        `out` a DeviceBuffer of at least 4 F C bytes on the block's device: written there and returned, the
+        posteriors stay in HBM.  `with_lse`: ``(posteriors, lse [F] float32 on the host)``, the per-frame
+        log-sum-exp of :meth:`accumulate`, bit for bit."""
+        self._check(dgmm)
+        F, n = self.nframes, dgmm.num_gauss
+        post = _backend.DeviceBuffer(4 * max(1, F * n), self.device) if out is None else out
+        if post.nbytes < 4 * F * n:
+            raise ValueError(f'out holds {post.nbytes} bytes, the posteriors need {4 * F * n}')
+        lse = _backend.DeviceBuffer(4 * max(1, F), self.device) if with_lse else None
+        _backend.check(_backend.lib().snf_gmm_posteriors(
+            self.device, C.c_void_p(self.frames.ptr), F, self.dim, *dgmm.args(), C.c_void_p(post.ptr), _p(lse), None))
+        result = post.download(np.empty((F, n), dtype=np.float32)) if out is None else post
+        return (result, lse.download(np.empty(F, dtype=np.float32))) if with_lse else result
+
     def accumulate(self, dgmm, with_lse=False):
         """E-step: (stats [C, 2D + 1] float64, tot_like, lse [F] float32 or None)"""
         self._check(dgmm)

@@ -41,10 +41,12 @@ import os
 
 import numpy as np
 
+from shennong_amd import _backend
 from shennong_amd import gmm as _gmm
 from shennong_amd import pipeline
 from shennong_amd.base import BaseProcessor
-from shennong_amd.features import FeaturesCollection
+from shennong_amd.device import DeviceFeaturesCollection
+from shennong_amd.features import Features, FeaturesCollection
 from shennong_amd.logger import null_logger
 from shennong_amd.postprocessor.cmvn import SlidingWindowCmvnPostProcessor
 from shennong_amd.postprocessor.vad import VadPostProcessor
@@ -426,6 +428,79 @@ class DiagUbmProcessor(BaseProcessor):
             bounds = zip([0] + cuts, cuts + [len(pairs)])
             out[utt] = [pairs[a:b] for a, b in bounds] if counts.size else []
         return out
+
+    def posteriorgrams(self, feats_collection, device=False):
+        """The posteriorgram of every utterance under the trained model: one probability per frame and Gaussian,
+        ``exp(L[f, c] - logsumexp_c L[f, :])``, float32 [nframes, num_gauss], with the input's times (an extension:
+        the reference hands out the pruned posteriors of a selection only, :meth:`gaussian_selection_to_post`).
+        No pruning, no smoothing.  Computed on the device over all the frames at once (snf_gmm_posteriors).
+
+        Parameters
+        ----------
+        feats_collection : FeaturesCollection or DeviceFeaturesCollection
+            The features the model was trained on (same dimension).  A device collection is read where it lies
+            and must lie in one block.
+        device : bool
+            True: a :class:`~shennong_amd.device.DeviceFeaturesCollection` over the block the kernel wrote,
+            for :func:`~shennong_amd.dtw_distances` or :func:`~shennong_amd.abx_scores` with
+            ``metric='symkl'`` or for ``padded()``.  False: its ``to_host()``.
+
+        The properties are the input's plus ``'posteriorgram': {'num_gauss': ..., 'ndims': ...}`` (`ndims` of
+        the source features).
+
+        Raises
+        ------
+        TypeError
+            If the model is not trained.
+        ValueError
+            If the features do not have the model's dimension, or lie in several device blocks.
+        """
+        self._check_gmm()
+        owned = None
+        if isinstance(feats_collection, DeviceFeaturesCollection):
+            source = feats_collection
+            source._alive()
+            if len(source._blocks) > 1:
+                raise ValueError('the utterances lie in {} device blocks (one per sample rate): posteriorgrams '
+                                 'are made of one block'.format(len(source._blocks)))
+        else:
+            source = owned = DeviceFeaturesCollection.from_host(feats_collection)
+        try:
+            names = list(source)
+            num_gauss, ndims = self.gmm.num_gauss(), self.gmm.dim()
+            extra = {'posteriorgram': {'num_gauss': num_gauss, 'ndims': ndims}}
+            template = FeaturesCollection()
+            for name in names:
+                feats = source[name]
+                shape = (feats.nframes, num_gauss)
+                placeholder = np.broadcast_to(np.float32(0), shape) if shape[0] else np.zeros(shape, np.float32)
+                # (the result copies times and properties when they are first read: the input's are not touched)
+                template[name] = Features._of_batch(placeholder, feats.times, feats.properties, extra)
+            if source._blocks:
+                in_block = source._blocks[0]
+                block = _gmm.FrameBlock.from_device(in_block.alive(), in_block.foff, in_block.dim)
+                order = in_block.names
+            else:
+                block, order = None, names
+            nframes = block.nframes if block is not None else 0
+            device_id = block.device if block is not None else None
+            out = _backend.DeviceBuffer(max(16, 4 * nframes * num_gauss), device_id)
+            try:
+                if nframes:
+                    block.posteriors(_gmm.DeviceGmm(self.gmm, block.device), out=out)
+                result = DeviceFeaturesCollection._build(template, [(out, order, num_gauss)])
+            except BaseException:
+                out.free()
+                raise
+        finally:
+            if owned is not None:
+                owned.release()
+        if device:
+            return result
+        try:
+            return result.to_host()
+        finally:
+            result.release()
 
     def accumulate(self, feats_collection, weights_collection=None, njobs=1):
         """Statistics for training a diagonal GMM (reference ubm.py:585-664, Kaldi gmm-global-acc-stats).

@@ -2,9 +2,10 @@
 """Times the DTW distances (snf_dtw_pairs, shennong_amd.dtw.dtw_distances) on one MI355X, one JSON line per
 workload.
 
-    python tools/time_dtw.py [a b c] [--repeat 7] [--metric cosine] [--out profiles/dtw_timing.jsonl]
+    python tools/time_dtw.py [a b c] [--repeat 7] [--metric cosine [symkl ...]] [--out profiles/dtw_timing.jsonl]
 
-Workloads (everything seeded; standard-normal float32 rows):
+Several metrics are timed one after the other in one process, a line each.  Workloads (everything seeded;
+standard-normal float32 rows; for symkl rows of probabilities, the float32 softmax of twice such rows):
   a  1 000 000 pairs among 20 000 items of 5 to 30 frames, D = 39 (word-sized ABX items, a task file's worth)
   b  100 000 pairs among 5 000 items of 30 to 100 frames, D = 39
   c  10 000 pairs among 400 items of 298 frames, D = 40 (whole 3-second utterances)
@@ -41,13 +42,16 @@ WORKLOADS = {
 }
 
 
-def make(spec, seed):
+def make(spec, seed, metric='cosine'):
     """(host collection of one utterance per item, items, pairs)"""
     import dtw_cases
     rng = np.random.default_rng(seed)
     lo, hi = spec['frames']
     frames = rng.integers(lo, hi + 1, size=spec['items'])
     block = rng.standard_normal((int(frames.sum()), spec['dim']), dtype=np.float32)
+    if metric == 'symkl':
+        block = np.exp(2 * block - 2 * block.max(axis=1, keepdims=True))
+        block /= block.sum(axis=1, keepdims=True)
     starts = np.concatenate([[0], np.cumsum(frames)[:-1]])
     feats = dtw_cases.collection([block[a:a + n] for a, n in zip(starts.tolist(), frames.tolist())])
     items = [('item%d' % k, 0.0, 1e9) for k in range(spec['items'])]
@@ -59,12 +63,13 @@ def median(values):
     return float(np.median(values))
 
 
-def run(name, args):
+def run(name, args, metric):
     from shennong_amd import _backend, dtw
     from shennong_amd.device import DeviceFeaturesCollection
     import dtw_f64
+    import symkl_f64
     spec = WORKLOADS[name]
-    feats, items, pairs, frames = make(spec, seed=ord(name))
+    feats, items, pairs, frames = make(spec, seed=ord(name), metric=metric)
     cells = int((frames[pairs[:, 0]].astype(np.int64) * frames[pairs[:, 1]]).sum())
     resident = DeviceFeaturesCollection.from_host(feats)
     first, count, pairs32, dim, block = dtw._select(resident, pairs, items)
@@ -78,7 +83,7 @@ def run(name, args):
     d_cost, d_len = _backend.DeviceBuffer(4 * n), _backend.DeviceBuffer(4 * n)
 
     def call():
-        _backend.dtw_pairs(block.buffer.ptr, dim, first, count, pairs32, args.metric, d_cost.ptr, d_len.ptr,
+        _backend.dtw_pairs(block.buffer.ptr, dim, first, count, pairs32, metric, d_cost.ptr, d_len.ptr,
                            stream=stream.value)
 
     call()
@@ -94,15 +99,15 @@ def run(name, args):
         ms = C.c_float()
         _backend.check(L.snf_event_elapsed_ms(ev[0], ev[1], C.byref(ms)))
         event_ms.append(ms.value)
-    dtw.dtw_distances(resident, pairs, items=items, metric=args.metric)
+    dtw.dtw_distances(resident, pairs, items=items, metric=metric)
     wall_ms = []
     for _ in range(args.repeat):
         t0 = time.perf_counter()
-        got = dtw.dtw_distances(resident, pairs, items=items, metric=args.metric)
+        got = dtw.dtw_distances(resident, pairs, items=items, metric=metric)
         wall_ms.append(1e3 * (time.perf_counter() - t0))
     assert np.isfinite(got).all()
     line = {
-        'workload': name, 'metric': args.metric, 'device': _backend.device_name(0), 'pairs': n, 'cells': cells,
+        'workload': name, 'metric': metric, 'device': _backend.device_name(0), 'pairs': n, 'cells': cells,
         'items': spec['items'], 'frames': list(spec['frames']), 'dim': spec['dim'], 'repeat': args.repeat,
         'event_ms': sorted(event_ms), 'call_ms': sorted(call_ms), 'wall_ms': sorted(wall_ms),
         'event_median_ms': median(event_ms), 'call_median_ms': median(call_ms), 'wall_median_ms': median(wall_ms),
@@ -113,7 +118,8 @@ def run(name, args):
         t0 = time.perf_counter()
         want = []
         for a, b in pairs[:20].tolist():
-            want.append(dtw_f64.dtw(feats['item%d' % a].data, feats['item%d' % b].data, args.metric)[0])
+            x, y = feats['item%d' % a].data, feats['item%d' % b].data
+            want.append(symkl_f64.dtw(x, y)[0] if metric == 'symkl' else dtw_f64.dtw(x, y, metric)[0])
         line['statement_f64_ms_per_pair'] = 1e3 * (time.perf_counter() - t0) / 20
         line['statement_max_abs_difference_20_pairs'] = float(np.abs(got[:20] - np.array(want)).max())
     for e in ev:
@@ -128,17 +134,18 @@ def main():
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('workloads', nargs='*', help='a, b, c (default: all)')
     parser.add_argument('--repeat', type=int, default=7)
-    parser.add_argument('--metric', default='cosine')
+    parser.add_argument('--metric', nargs='+', default=['cosine'])
     parser.add_argument('--out')
     args = parser.parse_args()
     if set(args.workloads) - set(WORKLOADS):
         parser.error('workloads are ' + ', '.join(sorted(WORKLOADS)))
     for name in args.workloads or sorted(WORKLOADS):
-        line = json.dumps(run(name, args))
-        print(line, flush=True)
-        if args.out:
-            with open(args.out, 'a') as fh:
-                fh.write(line + '\n')
+        for metric in args.metric:
+            line = json.dumps(run(name, args, metric))
+            print(line, flush=True)
+            if args.out:
+                with open(args.out, 'a') as fh:
+                    fh.write(line + '\n')
 
 
 if __name__ == '__main__':
