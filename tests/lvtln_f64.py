@@ -13,8 +13,9 @@ def frame_terms(sel, post, means_invvars, inv_vars):
     return (p[..., None] * mi).sum(axis=1), (p[..., None] * iv).sum(axis=1), p.sum(axis=1)
 
 
-def fmllr_stats(x, sel, post, means_invvars, inv_vars):
-    """(beta, K [D, D+1], G [D, D+1, D+1]) of one segment"""
+def fmllr_stats(x, sel, post, means_invvars, inv_vars, fast=False):
+    """(beta, K [D, D+1], G [D, D+1, D+1]) of one segment.  `fast`: G as one matrix product of b^T with the
+    frames' outer products x+ x+^T (the same float64 sums over the frames, for long segments at large D)"""
     x = np.asarray(x, np.float64)
     D = x.shape[1]
     if x.shape[0] == 0:
@@ -22,6 +23,9 @@ def fmllr_stats(x, sel, post, means_invvars, inv_vars):
     a, b, count = frame_terms(sel, post, means_invvars, inv_vars)
     xp = np.concatenate([x, np.ones((x.shape[0], 1))], axis=1)
     K = a.T @ xp
+    if fast:
+        outer = (xp[:, :, None] * xp[:, None, :]).reshape(x.shape[0], -1)
+        return float(count.sum()), K, (b.T @ outer).reshape(D, D + 1, D + 1)
     G = np.einsum('fd,fk,fl->dkl', b, xp, xp)
     return float(count.sum()), K, G
 
@@ -45,12 +49,15 @@ def fmllr_stats_loop(x, sel, post, means_invvars, inv_vars):
     return beta, K, G
 
 
-def apply_transform_to_stats(A, stats):
-    """ApplyFeatureTransformToStats with A [D, D] (or [D, D+1])"""
+def apply_transform_to_stats(A, stats, fast=False):
+    """ApplyFeatureTransformToStats with A [D, D] (or [D, D+1]).  `fast`: G'_d = (Ahat G_d) Ahat^T as two
+    matrix products per row instead of the five-index sum (the same sums in another association: large D)"""
     beta, K, G = stats
     D = K.shape[0]
     Ah = np.eye(D + 1)
     Ah[:D, :A.shape[1]] = A
+    if fast:
+        return beta, K @ Ah.T, np.matmul(np.matmul(Ah, G), Ah.T)
     return beta, K @ Ah.T, np.einsum('ik,dkl,jl->dij', Ah, G, Ah)
 
 
@@ -92,8 +99,9 @@ def compose(T, A):
     return np.concatenate([T[:, :D] @ A, T[:, D:]], axis=1)
 
 
-def compute_transform(As, logdets, stats, norm_type, logdet_scale, default_class):
-    """LinearVtln::ComputeTransform: (objectives [C], class, impr, count, W [D, D+1])"""
+def compute_transform(As, logdets, stats, norm_type, logdet_scale, default_class, fast=False):
+    """LinearVtln::ComputeTransform: (objectives [C], class, impr, count, W [D, D+1]).  `fast`: see
+    apply_transform_to_stats"""
     beta, K, G = stats
     D = K.shape[0]
     if beta == 0.0:
@@ -104,7 +112,7 @@ def compute_transform(As, logdets, stats, norm_type, logdet_scale, default_class
     objs, Ws = [], []
     for c, A in enumerate(As):
         A = np.asarray(A, np.float64)
-        st = apply_transform_to_stats(A, stats)
+        st = apply_transform_to_stats(A, stats, fast)
         if norm_type == 'none':
             T = ident
         elif norm_type == 'offset':
