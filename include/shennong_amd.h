@@ -749,6 +749,38 @@ int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t
                   const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
                   int32_t metric, float* d_cost, int32_t* d_len, void* stream);
 
+/* ---- Query-by-example search: subsequence DTW of queries in targets -------------------------------------------
+ * An extension with no reference call behind it.  It replaces the host double loop that a user of the features
+ * (MFCCs, or the posteriorgrams of snf_gmm_posteriors, which were introduced for this task) runs to find where a
+ * short query - a word, a segment of an alignment - occurs inside whole utterances: the pairs of one call are
+ * searched on the device from rows that lie in HBM.  The definition is this project's own (DESIGN 4.17,
+ * tests/dtw_search_f64.py); agreement with any outside toolkit is unpinned.
+ *
+ * Items, pairs, `metric` and the frame distance d are those of snf_dtw_pairs; of pair p = (query, target) the query
+ * x [N, dim] gives the rows of the lattice and the target y [M, dim] its columns:
+ *   C[0][j] = d[0][j], L[0][j] = 1, B[0][j] = j for every j                                      (free start)
+ *   i >= 1: C[i][j] = d[i][j] + C[q], L[i][j] = L[q] + 1, B[i][j] = B[q], q the predecessor of smallest C among
+ *   (i-1, j-1), (i-1, j), (i, j-1) that exist, ties to the first of that order;
+ *   score[j] = C[N-1][j] / (float)L[N-1][j] (the correctly rounded float32 division) if `normalized`, else
+ *   C[N-1][j]; end = the smallest j of minimal score (a strict < over ascending j)                   (free end)
+ *   d_end[p] = end, d_start[p] = B[N-1][end], d_cost[p] = C[N-1][end] (float32 sums), d_len[p] = L[N-1][end].
+ * The dynamic programme minimises C; `normalized` (0 or 1) only ranks the ends, which is why it is an argument here
+ * and not a division left to the caller.  Frames are counted from the target's first row.
+ * Curves: h_curve_first NULL (then the three d_curve_* are NULL too), or a HOST array of n_pairs element offsets:
+ * (C, L, B)[N-1][j] of pair p go to element h_curve_first[p] + j, j < M, of d_curve_cost, d_curve_len and
+ * d_curve_start; no other element of them is touched.  Limits: SNF_DTW_MAX_FRAMES rows per item (query or target),
+ * SNF_DTW_MAX_DIM.  Results are in the caller's pair order, every element of the four result arrays is written, and
+ * a pair's result does not depend on the other pairs of the call.  Non-finite features give undefined values,
+ * nothing worse.
+ * SNF_E_INVALID, before any device work: what snf_dtw_pairs refuses, `normalized` not 0 or 1, curve pointers
+ * partly set, a curve stretch below element 0, ending beyond element 2^31 or overlapping another pair's.
+ * n_pairs = 0 does nothing.  Streams, the slot of the tables and the symkl log block: as snf_dtw_pairs. */
+int snf_dtw_search(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                   const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs /* (query, target) */,
+                   int64_t n_pairs, int32_t metric, int32_t normalized, float* d_cost, int32_t* d_len,
+                   int32_t* d_start, int32_t* d_end, const int64_t* h_curve_first, float* d_curve_cost,
+                   int32_t* d_curve_len, int32_t* d_curve_start, void* stream);
+
 /* ---- ABX triplet counts over a table of distances (the two steps after the distances in the reference's examples) --
  * An extension with no reference call behind it: the reference's examples run `abx-score` and `abx-analyze` of an
  * external toolkit on the CPU (reference examples/features_abx/scripts/abx_score.sh:22-23), one triplet at a time,

@@ -49,7 +49,7 @@ EXPORTS = [
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
     'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
     'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs',
-    'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs', 'snf_abx_cells']
+    'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs', 'snf_dtw_search', 'snf_abx_cells']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -206,6 +206,8 @@ def lib():
         L.snf_collate_num_out.restype = i64
         L.snf_collate_padded.argtypes = [i32, vp, i32, pi64, i64, i32, i32, i32, i32, i32, f32, i64, vp, vp, vp]
         L.snf_dtw_pairs.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, vp, vp, vp]
+        L.snf_dtw_search.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, i32, vp, vp, vp, vp, pi64, vp, vp,
+                                     vp, vp]
         L.snf_abx_cells.argtypes = [i32, vp, vp, i64, pi64, i64, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
@@ -1055,6 +1057,34 @@ def dtw_pairs(d_rows, dim, item_first, item_count, pairs, metric, d_cost, d_len,
         first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int32)), first.shape[0],
         pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], DTW_METRICS[metric], C.c_void_p(d_cost),
         C.c_void_p(d_len), C.c_void_p(stream) if stream else None))
+
+
+def dtw_search(d_rows, dim, item_first, item_count, pairs, metric, normalized, d_cost, d_len, d_start, d_end,
+               curve_first=None, d_curve_cost=None, d_curve_len=None, d_curve_start=None, device=None, stream=None):
+    """Subsequence DTW of every (query, target) pair of `pairs` [P, 2] over the items of ``dtw_pairs``: cost
+    (float32), path length, start and end frame in the target (int32) of the best end at the four device pointers;
+    `curve_first` (host int64 [P], element offsets) with the three curve device pointers: (C, L, B) of every end
+    of pair p from element ``curve_first[p]``.  See snf_dtw_search in include/shennong_amd.h"""
+    first = np.ascontiguousarray(item_first, dtype=np.int64)
+    count = np.ascontiguousarray(item_count, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if metric not in DTW_METRICS:
+        raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(DTW_METRICS)))
+    curves = None
+    if curve_first is not None:
+        curves = np.ascontiguousarray(curve_first, dtype=np.int64).reshape(-1)
+        if curves.shape[0] != pairs.shape[0]:
+            raise ValueError('curve_first has {} entries for {} pairs'.format(curves.shape[0], pairs.shape[0]))
+        if curves.shape[0] == 0:   # (ctypes gives no address of an empty array: any non-null one says "curves")
+            curves = np.zeros(1, dtype=np.int64)
+    pointer = lambda d: C.c_void_p(d) if d else None   # noqa: E731
+    check(lib().snf_dtw_search(
+        _DEVICE if device is None else int(device), C.c_void_p(d_rows), int(dim),
+        first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int32)), first.shape[0],
+        pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], DTW_METRICS[metric], int(bool(normalized)),
+        C.c_void_p(d_cost), C.c_void_p(d_len), C.c_void_p(d_start), C.c_void_p(d_end),
+        curves.ctypes.data_as(C.POINTER(C.c_int64)) if curves is not None else None,
+        pointer(d_curve_cost), pointer(d_curve_len), pointer(d_curve_start), C.c_void_p(stream) if stream else None))
 
 
 def abx_cells(d_cost, d_len, n_dist, cells, d_counts, device=None, stream=None):

@@ -1,8 +1,11 @@
-// C ABI of libshennong_hip.so (include/shennong_amd.h): DTW cost and path length of pairs of feature items.  Every
-// argument is checked on the host before any device is asked for.  The host sorts the pairs by kernel class and,
-// within a class, by the cells of their lattice descending (kernels_dtw.hip).  The item and pair tables go up on the
-// calling thread's own stream (waited for) into a slot that stays reserved, with the row norms of the call, until
-// the kernels, enqueued on the caller's stream, have run - so the call does not wait for the caller's stream.
+// C ABI of libshennong_hip.so (include/shennong_amd.h): DTW cost and path length of pairs of feature items
+// (snf_dtw_pairs) and subsequence DTW search of queries in targets (snf_dtw_search).  Every argument is checked on
+// the host before any device is asked for.  The host sorts the pairs by kernel class and, within a class, by the
+// cells of their lattice descending (kernels_dtw.hip).  The item and pair tables go up on the calling thread's own
+// stream (waited for) into a slot that stays reserved, with the row norms of the call, until the kernels, enqueued
+// on the caller's stream, have run - so the call does not wait for the caller's stream.  Both calls share the
+// checks of the tables (check_tables), the sort (sort_pairs) and the slot protocol (enqueue).
+#include <algorithm>
 #include <memory>
 
 #include "plan.h"
@@ -14,7 +17,7 @@ namespace {
 // Device tables and scratch that kernels in flight may still be using: `done` is recorded behind them
 struct DtwSlot {
   int device = -1;
-  DevBuf items, pairs, aux;
+  DevBuf items, pairs, aux, curves;   // (curves: the curve offsets of a search, in the caller's pair order)
   hipEvent_t done = nullptr;
   bool taken = false;   // between take_slot and the event's record (or the failure that gives it back)
 };
@@ -46,84 +49,95 @@ void give_slot(DtwSlot* slot) {
   slot->taken = false;
 }
 
-}  // namespace
-
-extern "C" {
-
-int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
-                  const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
-                  int32_t metric, float* d_cost, int32_t* d_len, void* stream) {
-  if (dim < 1 || dim > kDtwMaxDim)
-    return set_error(SNF_E_INVALID, "dtw: dim must be in [1, " + std::to_string(kDtwMaxDim) + "]");
-  if (metric != SNF_DTW_COSINE && metric != SNF_DTW_SQEUCLIDEAN && metric != SNF_DTW_SYMKL)
-    return set_error(SNF_E_INVALID, "dtw: metric must be 0 (cosine), 1 (sqeuclidean) or 2 (symkl)");
-  if (n_items < 1 || n_items > 0x7fffffff) return set_error(SNF_E_INVALID, "dtw: number of items out of range");
-  if (n_pairs < 0 || n_pairs > 0x7fffffff) return set_error(SNF_E_INVALID, "dtw: number of pairs out of range");
-  if (!h_item_first || !h_item_count) return set_error(SNF_E_INVALID, "dtw: null item table");
-  std::vector<DtwItem> items(static_cast<size_t>(n_items));
-  int64_t row_lo = INT64_MAX, row_hi = 0;
-  for (int64_t t = 0; t < n_items; ++t) {
-    const int64_t first = h_item_first[t];
-    const int32_t count = h_item_count[t];
-    if (first < 0 || first > (int64_t(1) << 40))
-      return set_error(SNF_E_INVALID, "dtw: item " + std::to_string(t) + " starts outside the block");
-    if (count < 1) return set_error(SNF_E_INVALID, "dtw: item " + std::to_string(t) + " has no frames");
-    if (count > kDtwMaxFrames)
-      return set_error(SNF_E_INVALID, "dtw: item " + std::to_string(t) + " has " + std::to_string(count) +
-                                          " frames, the limit is " + std::to_string(kDtwMaxFrames));
-    items[t] = {first, count, 0};
-    row_lo = std::min(row_lo, first);
-    row_hi = std::max(row_hi, first + count);
-  }
-  if (row_hi - row_lo > 0x7fffffff)
-    return set_error(SNF_E_INVALID, "dtw: the items span 2^31 rows or more: compute them in parts");
-  if (n_pairs > 0 && !h_pairs) return set_error(SNF_E_INVALID, "dtw: null pair table");
-  std::vector<DtwPair> pairs(static_cast<size_t>(n_pairs));
+// The host tables of a call, checked
+struct DtwTables {
+  std::vector<DtwItem> items;
+  std::vector<DtwPair> pairs;   // x gives the rows of the lattice, y its columns: the class of the pair
   int64_t class_count[kDtwClasses] = {0, 0, 0};
+  int64_t row_lo = INT64_MAX, row_hi = 0;
+};
+
+// `who`: the prefix of the messages ("dtw", "dtw_search")
+int check_tables(const std::string& who, int32_t dim, int32_t metric, const int64_t* h_item_first,
+                 const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
+                 DtwTables& t) {
+  if (dim < 1 || dim > kDtwMaxDim)
+    return set_error(SNF_E_INVALID, who + ": dim must be in [1, " + std::to_string(kDtwMaxDim) + "]");
+  if (metric != SNF_DTW_COSINE && metric != SNF_DTW_SQEUCLIDEAN && metric != SNF_DTW_SYMKL)
+    return set_error(SNF_E_INVALID, who + ": metric must be 0 (cosine), 1 (sqeuclidean) or 2 (symkl)");
+  if (n_items < 1 || n_items > 0x7fffffff) return set_error(SNF_E_INVALID, who + ": number of items out of range");
+  if (n_pairs < 0 || n_pairs > 0x7fffffff) return set_error(SNF_E_INVALID, who + ": number of pairs out of range");
+  if (!h_item_first || !h_item_count) return set_error(SNF_E_INVALID, who + ": null item table");
+  t.items.resize(static_cast<size_t>(n_items));
+  for (int64_t k = 0; k < n_items; ++k) {
+    const int64_t first = h_item_first[k];
+    const int32_t count = h_item_count[k];
+    if (first < 0 || first > (int64_t(1) << 40))
+      return set_error(SNF_E_INVALID, who + ": item " + std::to_string(k) + " starts outside the block");
+    if (count < 1) return set_error(SNF_E_INVALID, who + ": item " + std::to_string(k) + " has no frames");
+    if (count > kDtwMaxFrames)
+      return set_error(SNF_E_INVALID, who + ": item " + std::to_string(k) + " has " + std::to_string(count) +
+                                          " frames, the limit is " + std::to_string(kDtwMaxFrames));
+    t.items[k] = {first, count, 0};
+    t.row_lo = std::min(t.row_lo, first);
+    t.row_hi = std::max(t.row_hi, first + count);
+  }
+  if (t.row_hi - t.row_lo > 0x7fffffff)
+    return set_error(SNF_E_INVALID, who + ": the items span 2^31 rows or more: compute them in parts");
+  if (n_pairs > 0 && !h_pairs) return set_error(SNF_E_INVALID, who + ": null pair table");
+  t.pairs.resize(static_cast<size_t>(n_pairs));
   for (int64_t p = 0; p < n_pairs; ++p) {
     const int32_t x = h_pairs[2 * p], y = h_pairs[2 * p + 1];
     if (x < 0 || x >= n_items || y < 0 || y >= n_items)
-      return set_error(SNF_E_INVALID, "dtw: pair " + std::to_string(p) + " (" + std::to_string(x) + ", " +
+      return set_error(SNF_E_INVALID, who + ": pair " + std::to_string(p) + " (" + std::to_string(x) + ", " +
                                           std::to_string(y) + ") is out of range for " + std::to_string(n_items) +
                                           " items");
-    pairs[p] = {x, y, static_cast<int32_t>(p), items[x].frames * items[y].frames};   // (at most 2^24 cells)
-    ++class_count[dtw_class_of(items[y].frames)];
+    t.pairs[p] = {x, y, static_cast<int32_t>(p), t.items[x].frames * t.items[y].frames};   // (at most 2^24 cells)
+    ++t.class_count[dtw_class_of(t.items[y].frames)];
   }
-  if (n_pairs == 0) return SNF_OK;
-  if (!d_rows || (reinterpret_cast<uintptr_t>(d_rows) & 3))
-    return set_error(SNF_E_INVALID, "dtw: d_rows is null or not aligned to float32");
-  if (!d_cost || !d_len || (reinterpret_cast<uintptr_t>(d_cost) & 3) || (reinterpret_cast<uintptr_t>(d_len) & 3))
-    return set_error(SNF_E_INVALID, "dtw: d_cost or d_len is null or not 4-byte aligned");
-  // by class, within a class the largest lattice first, equal ones in the caller's order: a stable radix sort of
-  // the 27-bit key (class, 2^24 - cells), 9 bits a pass (a million pairs: milliseconds, where std::sort with a
-  // comparator that looks the items up takes a tenth of a second)
-  {
-    const uint32_t top = uint32_t(kDtwMaxFrames) * kDtwMaxFrames;
-    auto key_of = [&](const DtwPair& p) {
-      return (uint32_t(dtw_class_of(items[p.y].frames)) << 25) | (top - uint32_t(p.cells));
-    };
-    std::vector<uint32_t> keys(pairs.size()), keys_next(pairs.size());
-    for (size_t p = 0; p < pairs.size(); ++p) keys[p] = key_of(pairs[p]);
-    std::vector<DtwPair> next(pairs.size());
-    for (int shift = 0; shift < 27; shift += 9) {
-      size_t start[513] = {0};
-      for (uint32_t k : keys) ++start[((k >> shift) & 511) + 1];
-      for (int b = 0; b < 512; ++b) start[b + 1] += start[b];
-      for (size_t p = 0; p < pairs.size(); ++p) {
-        const size_t to = start[(keys[p] >> shift) & 511]++;
-        next[to] = pairs[p];
-        keys_next[to] = keys[p];
-      }
-      pairs.swap(next);
-      keys.swap(keys_next);
+  return SNF_OK;
+}
+
+// by class, within a class the largest lattice first, equal ones in the caller's order: a stable radix sort of
+// the 27-bit key (class, 2^24 - cells), 9 bits a pass (a million pairs: milliseconds, where std::sort with a
+// comparator that looks the items up takes a tenth of a second)
+int sort_pairs(const std::string& who, DtwTables& t) {
+  std::vector<DtwPair>& pairs = t.pairs;
+  const std::vector<DtwItem>& items = t.items;
+  const uint32_t top = uint32_t(kDtwMaxFrames) * kDtwMaxFrames;
+  auto key_of = [&](const DtwPair& p) {
+    return (uint32_t(dtw_class_of(items[p.y].frames)) << 25) | (top - uint32_t(p.cells));
+  };
+  std::vector<uint32_t> keys(pairs.size()), keys_next(pairs.size());
+  for (size_t p = 0; p < pairs.size(); ++p) keys[p] = key_of(pairs[p]);
+  std::vector<DtwPair> next(pairs.size());
+  for (int shift = 0; shift < 27; shift += 9) {
+    size_t start[513] = {0};
+    for (uint32_t k : keys) ++start[((k >> shift) & 511) + 1];
+    for (int b = 0; b < 512; ++b) start[b + 1] += start[b];
+    for (size_t p = 0; p < pairs.size(); ++p) {
+      const size_t to = start[(keys[p] >> shift) & 511]++;
+      next[to] = pairs[p];
+      keys_next[to] = keys[p];
     }
-    // (a kernel class sizes its seam row by the class: no pair may sit in another class's stretch)
-    int64_t p = 0;
-    for (int c = 0; c < kDtwClasses; ++c)
-      for (const int64_t end = p + class_count[c]; p < end; ++p)
-        if (dtw_class_of(items[pairs[p].y].frames) != c)
-          return set_error(SNF_E_RUNTIME, "dtw: internal error, the pairs are not sorted by class");
+    pairs.swap(next);
+    keys.swap(keys_next);
   }
+  // (a kernel class sizes its seam row by the class: no pair may sit in another class's stretch)
+  int64_t p = 0;
+  for (int c = 0; c < kDtwClasses; ++c)
+    for (const int64_t end = p + t.class_count[c]; p < end; ++p)
+      if (dtw_class_of(items[pairs[p].y].frames) != c)
+        return set_error(SNF_E_RUNTIME, who + ": internal error, the pairs are not sorted by class");
+  return SNF_OK;
+}
+
+// Takes a slot, uploads the tables (and `curve_first`, the curve offsets of a search, where given), sizes the aux
+// block and calls `launch(slot, compute_units, stream)`, which enqueues the kernels; records the slot's event behind
+// them
+template <class Launch>
+int enqueue(const std::string& who, int device_id, void* stream, const DtwTables& t, int32_t dim, int32_t metric,
+            const std::vector<int64_t>* curve_first, Launch&& launch) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return set_error(SNF_E_NODEVICE, "no HIP device visible: libshennong_hip needs an MI355X (gfx950)");
@@ -139,14 +153,14 @@ int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t
   if (!slot) return SNF_E_HIP;
   hipStream_t s = stream ? static_cast<hipStream_t>(stream) : mine->stream;
   // (DevBuf::upload waits for the copy on the thread's own stream: the tables are pageable vectors that go away)
-  int rc = slot->items.upload(items, mine->stream);
-  if (!rc) rc = slot->pairs.upload(pairs, mine->stream);
+  int rc = slot->items.upload(t.items, mine->stream);
+  if (!rc) rc = slot->pairs.upload(t.pairs, mine->stream);
+  if (!rc && curve_first) rc = slot->curves.upload(*curve_first, mine->stream);
   // (symkl: the log block of the row range too; a failed allocation ends the call before any kernel)
-  if (!rc) rc = slot->aux.ensure(sizeof(float) * dtw_aux_floats(row_hi - row_lo, dim, metric));
-  if (!rc)
-    rc = launch_dtw_pairs(d_rows, dim, slot->items.as<DtwItem>(), slot->pairs.as<DtwPair>(), class_count, row_lo,
-                          row_hi, slot->aux.as<float>(), metric, compute_units, d_cost, d_len, s);
-  if (!rc && hipEventRecord(slot->done, s) != hipSuccess) rc = set_error(SNF_E_HIP, "dtw: hipEventRecord failed");
+  if (!rc) rc = slot->aux.ensure(sizeof(float) * dtw_aux_floats(t.row_hi - t.row_lo, dim, metric));
+  if (!rc) rc = launch(*slot, compute_units, s);
+  if (!rc && hipEventRecord(slot->done, s) != hipSuccess)
+    rc = set_error(SNF_E_HIP, who + ": hipEventRecord failed");
   if (rc) {
     // (whatever was enqueued has finished before the slot's tables can be written again)
     (void)hipStreamSynchronize(s);
@@ -154,8 +168,86 @@ int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t
     return rc;
   }
   give_slot(slot);   // (free for the next call once `done` has completed: take_slot asks the event)
-  if (!stream && hipStreamSynchronize(s) != hipSuccess) return set_error(SNF_E_HIP, "dtw kernel failed");
+  if (!stream && hipStreamSynchronize(s) != hipSuccess) return set_error(SNF_E_HIP, who + " kernel failed");
   return SNF_OK;
+}
+
+bool bad_word_pointer(const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 3); }
+
+}  // namespace
+
+extern "C" {
+
+int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                  const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
+                  int32_t metric, float* d_cost, int32_t* d_len, void* stream) {
+  const std::string who = "dtw";
+  DtwTables t;
+  if (const int rc = check_tables(who, dim, metric, h_item_first, h_item_count, n_items, h_pairs, n_pairs, t))
+    return rc;
+  if (n_pairs == 0) return SNF_OK;
+  if (bad_word_pointer(d_rows)) return set_error(SNF_E_INVALID, "dtw: d_rows is null or not aligned to float32");
+  if (bad_word_pointer(d_cost) || bad_word_pointer(d_len))
+    return set_error(SNF_E_INVALID, "dtw: d_cost or d_len is null or not 4-byte aligned");
+  if (const int rc = sort_pairs(who, t)) return rc;
+  return enqueue(who, device_id, stream, t, dim, metric, nullptr, [&](DtwSlot& slot, int compute_units, hipStream_t s) {
+    return launch_dtw_pairs(d_rows, dim, slot.items.as<DtwItem>(), slot.pairs.as<DtwPair>(), t.class_count, t.row_lo,
+                            t.row_hi, slot.aux.as<float>(), metric, compute_units, d_cost, d_len, s);
+  });
+}
+
+int snf_dtw_search(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                   const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
+                   int32_t metric, int32_t normalized, float* d_cost, int32_t* d_len, int32_t* d_start,
+                   int32_t* d_end, const int64_t* h_curve_first, float* d_curve_cost, int32_t* d_curve_len,
+                   int32_t* d_curve_start, void* stream) {
+  const std::string who = "dtw_search";
+  DtwTables t;
+  if (const int rc = check_tables(who, dim, metric, h_item_first, h_item_count, n_items, h_pairs, n_pairs, t))
+    return rc;
+  if (normalized != 0 && normalized != 1) return set_error(SNF_E_INVALID, who + ": normalized must be 0 or 1");
+  const int curve_pointers = (h_curve_first != nullptr) + (d_curve_cost != nullptr) + (d_curve_len != nullptr) +
+                             (d_curve_start != nullptr);
+  if (curve_pointers != 0 && curve_pointers != 4)
+    return set_error(SNF_E_INVALID, who + ": the curve pointers must be all set or all null");
+  if (n_pairs == 0) return SNF_OK;
+  if (bad_word_pointer(d_rows))
+    return set_error(SNF_E_INVALID, who + ": d_rows is null or not aligned to float32");
+  if (bad_word_pointer(d_cost) || bad_word_pointer(d_len) || bad_word_pointer(d_start) || bad_word_pointer(d_end))
+    return set_error(SNF_E_INVALID, who + ": d_cost, d_len, d_start or d_end is null or not 4-byte aligned");
+  std::vector<int64_t> curve_first;
+  if (curve_pointers) {
+    if (bad_word_pointer(d_curve_cost) || bad_word_pointer(d_curve_len) || bad_word_pointer(d_curve_start))
+      return set_error(SNF_E_INVALID, who + ": a curve array is not 4-byte aligned");
+    // pair p owns the elements [first, first + M) of the three curve arrays: inside [0, 2^31), and no two overlap
+    curve_first.assign(h_curve_first, h_curve_first + n_pairs);
+    std::vector<std::pair<int64_t, int32_t>> stretch(static_cast<size_t>(n_pairs));   // (first, pair)
+    for (int64_t p = 0; p < n_pairs; ++p) {
+      const int64_t first = curve_first[p], columns = t.items[h_pairs[2 * p + 1]].frames;
+      if (first < 0 || first + columns > (int64_t(1) << 31))
+        return set_error(SNF_E_INVALID, who + ": the curve of pair " + std::to_string(p) + " (" +
+                                            std::to_string(columns) + " elements at " + std::to_string(first) +
+                                            ") lies outside [0, 2^31)");
+      stretch[p] = {first, static_cast<int32_t>(p)};
+    }
+    std::sort(stretch.begin(), stretch.end());
+    for (int64_t k = 0; k + 1 < n_pairs; ++k) {
+      const int32_t a = stretch[k].second, b = stretch[k + 1].second;
+      if (stretch[k].first + t.items[h_pairs[2 * a + 1]].frames > stretch[k + 1].first)
+        return set_error(SNF_E_INVALID, who + ": the curves of the pairs " + std::to_string(std::min(a, b)) +
+                                            " and " + std::to_string(std::max(a, b)) + " overlap");
+    }
+  }
+  if (const int rc = sort_pairs(who, t)) return rc;
+  return enqueue(who, device_id, stream, t, dim, metric, curve_pointers ? &curve_first : nullptr,
+                 [&](DtwSlot& slot, int compute_units, hipStream_t s) {
+                   const DtwSearchOut out = {d_cost, d_len, d_start, d_end,
+                                             curve_pointers ? slot.curves.as<int64_t>() : nullptr,
+                                             d_curve_cost, d_curve_len, d_curve_start};
+                   return launch_dtw_search(d_rows, dim, slot.items.as<DtwItem>(), slot.pairs.as<DtwPair>(),
+                                            t.class_count, t.row_lo, t.row_hi, slot.aux.as<float>(), metric,
+                                            normalized, compute_units, out, s);
+                 });
 }
 
 }  // extern "C"

@@ -421,6 +421,21 @@ size_t dtw_aux_floats(int64_t n_rows, int dim, int metric);
 int launch_dtw_pairs(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
                      const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
                      int compute_units, float* cost, int32_t* len, hipStream_t stream);
+// the pre-pass alone: the norms (symkl: h and the logarithms) of the rows [row_lo, row_hi) into `d_aux`
+int launch_dtw_rows(const float* rows, int dim, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
+                    hipStream_t stream);
+// kernels_dtw_search.hip: subsequence DTW of a query (x of the pair: the rows of the lattice) in a target (y: its
+// columns, which decide the class), free start and free end (snf_dtw_search).  Tables and `d_aux` as above.
+struct DtwSearchOut {
+  float* cost;                   // [P] in the caller's pair order, as len, start, end
+  int32_t *len, *start, *end;
+  const int64_t* curve_first;    // device copy of the caller's element offsets [P], or null: no curves
+  float* curve_cost;             // C, L, B of every end j of pair p at element curve_first[p] + j
+  int32_t *curve_len, *curve_start;
+};
+int launch_dtw_search(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
+                      const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
+                      int normalized, int compute_units, const DtwSearchOut& out, hipStream_t stream);
 
 // kernels_abx.hip: ABX triplet counts per cell over a table of distances (snf_abx_cells)
 constexpr int kAbxTile = 1024;        // floats of a B-row staged in LDS at a time (4 KB per wave)

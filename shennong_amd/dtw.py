@@ -24,6 +24,14 @@ For the items x [N, D] and y [M, D] of a pair, with d[i, j] the frame distance o
 
 The definition is this project's own (tests/dtw_f64.py and tests/symkl_f64.py state it in float64); agreement with
 the external toolkit, its KL divergence included, is not pinned (DESIGN sections 4.14 and 4.16).
+
+:func:`dtw_search` is the other classic use of the same rows, query-by-example search: where does a short query
+occur inside whole utterances?  The same lattice with a free start and a free end in the target (subsequence DTW,
+snf_dtw_search; its docstring has the definition, DESIGN section 4.17 the rest):
+
+    found = dtw_search(feats, queries=[('utt1', 0.31, 0.52)], targets=['utt2', 'utt3'])    # a DtwMatches
+    best = found.ranked(0)[0]                         # the pair of query 0 with the smallest score
+    found.target[best], found.onset[best], found.offset[best]
 """
 
 import numpy as np
@@ -31,7 +39,7 @@ import numpy as np
 from shennong_amd import _backend
 from shennong_amd.device import DeviceFeaturesCollection
 
-__all__ = ['dtw_distances', 'MAX_FRAMES']
+__all__ = ['dtw_distances', 'dtw_search', 'DtwMatches', 'MAX_FRAMES']
 
 MAX_FRAMES = _backend.DTW_MAX_FRAMES
 
@@ -67,6 +75,20 @@ def _layout(features):
     return first, dims[0] if dims else 0, None
 
 
+def _item_rows(features, first_of, centres, kind, k, item):
+    """(first row in the block, row count) of the item ``(name, onset, offset)``: the run of rows of the utterance
+    whose centre time lies in [onset, offset].  `centres` caches the centre times per name; `kind` and `k` name the
+    item in the error ('item 3', 'query 0')"""
+    name, onset, offset = item
+    if name not in first_of:
+        raise ValueError(f'{kind} {k}: utterance "{name}" is not in the collection')
+    if name not in centres:
+        centres[name] = _centres(features[name].times)
+    lo = int(np.searchsorted(centres[name], float(onset), side='left'))
+    hi = int(np.searchsorted(centres[name], float(offset), side='right'))
+    return first_of[name] + lo, max(hi - lo, 0)
+
+
 def _select(features, pairs, items):
     """(first row, row count) of every item and the pairs as an int32 array [P, 2] into them, all checked"""
     first_of, dim, block = _layout(features)
@@ -93,14 +115,7 @@ def _select(features, pairs, items):
         count = np.zeros(len(items), dtype=np.int64)
         centres = {}
         for k, item in enumerate(items):
-            name, onset, offset = item
-            if name not in first_of:
-                raise ValueError(f'item {k}: utterance "{name}" is not in the collection')
-            if name not in centres:
-                centres[name] = _centres(features[name].times)
-            lo = int(np.searchsorted(centres[name], float(onset), side='left'))
-            hi = int(np.searchsorted(centres[name], float(offset), side='right'))
-            first[k], count[k] = first_of[name] + lo, max(hi - lo, 0)
+            first[k], count[k] = _item_rows(features, first_of, centres, 'item', k, item)
         what = ['item {} ("{}", {}, {})'.format(k, *item) for k, item in enumerate(items)]
         pairs = np.asarray(pairs)
         if pairs.size == 0:
@@ -162,3 +177,193 @@ def dtw_distances(features, pairs, items=None, metric='cosine', normalized=True,
                 owned.release()
     distances = cost / lengths.astype(np.float32) if normalized and n_pairs else cost
     return (distances, lengths) if return_lengths else distances
+
+
+class DtwMatches:
+    """The best match of every (query, target) pair of a :func:`dtw_search`: numpy columns [P] in the order of
+    the pairs
+
+    `query`, `target` (int32): indices into the queries and the targets of the call.  `score`, `cost` (float32):
+    the score of the best end (the cost over the length if normalized, else the cost) and the cost of its path.
+    `length`, `start_frame`, `end_frame` (int32): the cells of the path, its first and its last frame, counted from
+    the first row of the target item.  `onset`, `offset` (float64 seconds): the start time of the start row and
+    the stop time of the end row of the target utterance ([n, 2] times), or their single time ([n] times)."""
+
+    columns = ('query', 'target', 'score', 'cost', 'length', 'start_frame', 'end_frame', 'onset', 'offset')
+
+    def __init__(self, query, target, score, cost, length, start_frame, end_frame, onset, offset, curves=None):
+        self.query = np.asarray(query, dtype=np.int32)
+        self.target = np.asarray(target, dtype=np.int32)
+        self.score = np.asarray(score, dtype=np.float32)
+        self.cost = np.asarray(cost, dtype=np.float32)
+        self.length = np.asarray(length, dtype=np.int32)
+        self.start_frame = np.asarray(start_frame, dtype=np.int32)
+        self.end_frame = np.asarray(end_frame, dtype=np.int32)
+        self.onset = np.asarray(onset, dtype=np.float64)
+        self.offset = np.asarray(offset, dtype=np.float64)
+        sizes = {getattr(self, name).shape for name in self.columns}
+        if len(sizes) != 1 or len(next(iter(sizes))) != 1:
+            raise ValueError('the columns must be one-dimensional and of one length: {}'.format(sorted(sizes)))
+        # (first [P + 1], cost, length, start): pair p owns the elements first[p] .. first[p + 1] of the three
+        self._curves = curves
+
+    def __len__(self):
+        return self.query.shape[0]
+
+    def curve(self, p):
+        """``(cost [M], length [M], start [M])`` of pair `p`: C, L and B of the path that ends at every frame of the
+        target (the score of an end is ``cost / length`` in float32, or ``cost``).  The material for several
+        detections per pair.  ValueError when the search did not ask for curves"""
+        if self._curves is None:
+            raise ValueError('no curves: call dtw_search with return_curves=True')
+        if not -len(self) <= p < len(self):
+            raise IndexError('pair {} is out of range for {} pairs'.format(p, len(self)))
+        first, cost, length, start = self._curves
+        p = p % len(self)
+        lo, hi = int(first[p]), int(first[p + 1])
+        return cost[lo:hi], length[lo:hi], start[lo:hi]
+
+    def ranked(self, query):
+        """The indices of the pairs of query `query` by ascending score, equal scores in the order of the pairs"""
+        mine = np.flatnonzero(self.query == query)
+        return mine[np.argsort(self.score[mine], kind='stable')]
+
+
+def _select_search(features, queries, targets, pairs):
+    """The queries then the targets as items (first row, row count), the pairs as an int32 array [P, 2] of (query
+    index, target index), and per target its utterance and its first row in it - all checked"""
+    first_of, dim, block = _layout(features)
+    centres = {}
+    first, count, what, where = [], [], [], []
+    sizes = []
+    for kind, entries in (('query', queries), ('target', targets)):
+        entries = list(entries)
+        sizes.append(len(entries))
+        for k, entry in enumerate(entries):
+            if isinstance(entry, str):
+                if entry not in first_of:
+                    raise ValueError(f'{kind} {k}: utterance "{entry}" is not in the collection')
+                name, rows = entry, (first_of[entry], features[entry].nframes)
+                what.append('{} {} ("{}")'.format(kind, k, entry))
+            else:
+                entry = tuple(entry)
+                if len(entry) != 3:
+                    raise ValueError('{} {}: not an utterance name or (name, onset, offset): {}'.format(kind, k, entry))
+                name, rows = entry[0], _item_rows(features, first_of, centres, kind, k, entry)
+                what.append('{} {} ("{}", {}, {})'.format(kind, k, *entry))
+            first.append(rows[0])
+            count.append(rows[1])
+            where.append((name, rows[0] - first_of[name]))
+    n_queries, n_targets = sizes
+    if pairs is None:   # every query against every target, query-major
+        pairs = np.stack(np.meshgrid(np.arange(n_queries), np.arange(n_targets), indexing='ij'), axis=-1)
+        pairs = pairs.reshape(-1, 2)
+    else:
+        pairs = np.asarray(pairs)
+        if pairs.size == 0:
+            pairs = np.zeros((0, 2), dtype=np.int32)
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in 'iu':
+            raise ValueError('pairs must be an integer array [P, 2] of (query index, target index)')
+        bad = np.argwhere((pairs < 0) | (pairs >= np.array([n_queries, n_targets])))
+        if bad.size:
+            p = int(bad[0, 0])
+            raise ValueError('pair {} ({}, {}) is out of range for {} queries and {} targets'.format(
+                p, int(pairs[p, 0]), int(pairs[p, 1]), n_queries, n_targets))
+    pairs = pairs.astype(np.int32)
+    count = np.array(count, dtype=np.int64)
+    for k in np.flatnonzero(count < 1).tolist()[:1]:
+        raise ValueError('{} has no frames'.format(what[k]))
+    for k in np.flatnonzero(count > MAX_FRAMES).tolist()[:1]:
+        raise ValueError('{} has {} frames, the limit is {}'.format(what[k], int(count[k]), MAX_FRAMES))
+    return (np.array(first, dtype=np.int64), count.astype(np.int32), pairs, n_queries, where[n_queries:], dim, block)
+
+
+def dtw_search(features, queries, targets, pairs=None, metric='cosine', normalized=True, return_curves=False):
+    """Query-by-example search: where does every query occur in every target?  Subsequence DTW on the GPU
+    (snf_dtw_search), a :class:`DtwMatches` with the best match of every (query, target) pair
+
+    For the query x [N, D] and the target y [M, D] of a pair, with d[i, j] the frame distance of the module's
+    docstring, the start and the end of the path in the target are free:
+
+        C[0, j] = d[0, j], L[0, j] = 1, B[0, j] = j for every j
+        i >= 1: C[i, j] = d[i, j] + C[p], L[i, j] = L[p] + 1, B[i, j] = B[p], p the predecessor of smallest C among
+        (i-1, j-1), (i-1, j), (i, j-1) that exist, ties to the first of that order
+        score[j] = C[N-1, j] / L[N-1, j] (float32 division) if normalized else C[N-1, j]
+        end_frame = the smallest j of minimal score, start_frame = B[N-1, end_frame], cost and length of that cell
+
+    As in :func:`dtw_distances` the dynamic programme minimises the cost C; the normalisation only ranks the ends,
+    it does not look for the path of smallest mean.  The definition is this project's own (tests/dtw_search_f64.py
+    states it in float64); agreement with any outside toolkit is not pinned.
+
+    `features`: a :class:`DeviceFeaturesCollection` (the rows are used where they lie), or a host
+    :class:`FeaturesCollection`, uploaded once.  Queries and targets lie in the one collection: a user with keyword
+    examples from elsewhere builds one collection of both.
+    `queries`, `targets`: sequences whose entries are an utterance name (all of its rows) or ``(name, onset,
+    offset)`` in seconds (the run of rows whose centre time lies in [onset, offset], as the items of
+    ``dtw_distances``).
+    `pairs` None: every query against every target, query-major.  Otherwise an integer array [P, 2] of (query
+    index, target index).
+    `return_curves`: keep (C, L, B) of every end of every pair for ``DtwMatches.curve``.
+
+    ValueError, before any device work: an unknown metric, a name that is not in the collection, an index out of
+    range, an item without frames or of more than ``MAX_FRAMES`` frames, items of different ndims, a collection in
+    several device blocks, curves of 2^31 elements or more."""
+    if metric not in _backend.DTW_METRICS:
+        raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(_backend.DTW_METRICS)))
+    first, count, pairs, n_queries, where, dim, block = _select_search(features, queries, targets, pairs)
+    n_pairs = pairs.shape[0]
+    columns = count[n_queries + pairs[:, 1]].astype(np.int64)   # M of every pair
+    curve_first = np.concatenate([[0], np.cumsum(columns)]).astype(np.int64)
+    total = int(curve_first[-1])
+    if return_curves and total >= 2 ** 31:
+        raise ValueError('the curves of the {} pairs hold {} elements, the limit is 2^31 - 1: search in parts'.format(
+            n_pairs, total))
+    cost = np.zeros(n_pairs, dtype=np.float32)
+    length, start, end = (np.zeros(n_pairs, dtype=np.int32) for _ in range(3))
+    curves = None
+    if return_curves:
+        curves = (curve_first, np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.int32),
+                  np.zeros(total, dtype=np.int32))
+    if n_pairs:
+        owned = None
+        if block is None:
+            owned = DeviceFeaturesCollection.from_host(features)
+            block = owned._blocks[0]
+        buffers = []
+        try:
+            buffer = block.alive()
+            for _ in range(4):
+                buffers.append(_backend.DeviceBuffer(4 * n_pairs, buffer.device))
+            if return_curves:
+                for _ in range(3):
+                    buffers.append(_backend.DeviceBuffer(4 * total, buffer.device))
+            index_pairs = pairs + np.array([0, n_queries], dtype=np.int32)   # (the targets lie behind the queries)
+            _backend.dtw_search(buffer.ptr, dim, first, count, index_pairs, metric, normalized,
+                                *[b.ptr for b in buffers[:4]],
+                                **(dict(curve_first=curve_first[:-1], d_curve_cost=buffers[4].ptr,
+                                        d_curve_len=buffers[5].ptr, d_curve_start=buffers[6].ptr)
+                                   if return_curves else {}),
+                                device=buffer.device)
+            for b, out in zip(buffers, (cost, length, start, end) + (curves[1:] if return_curves else ())):
+                b.download(out)
+        finally:
+            for b in buffers:
+                b.free()
+            if owned is not None:
+                owned.release()
+    score = cost / length.astype(np.float32) if normalized and n_pairs else cost.copy()
+    # the times of the matches: the start and stop times of the targets' utterances laid end to end, and per target
+    # the place of its first row in them
+    placed, begins, ends, rows = {}, [np.zeros(0)], [np.zeros(0)], 0
+    base = np.zeros(len(where), dtype=np.int64)
+    for t, (name, row) in enumerate(where):
+        if name not in placed:
+            stamps = np.asarray(features[name].times, dtype=np.float64)
+            begins.append(stamps[:, 0] if stamps.ndim == 2 else stamps)
+            ends.append(stamps[:, 1] if stamps.ndim == 2 else stamps)
+            placed[name] = rows
+            rows += stamps.shape[0]
+        base[t] = placed[name] + row
+    at = base[pairs[:, 1]] if n_pairs else np.zeros(0, dtype=np.int64)
+    onset, offset = np.concatenate(begins)[at + start], np.concatenate(ends)[at + end]
+    return DtwMatches(pairs[:, 0], pairs[:, 1], score, cost, length, start, end, onset, offset, curves)
