@@ -1,16 +1,8 @@
 // BUT/Phonexia bottleneck feature extractor (reference processor/bottleneck.py:403-764): voice activity
 // detection, the HTK log-mel front end, the Hamming-DCT context projection and the two stacked networks.
 //
-// Dense layer (bn_dense_kernel): Y = act(A W + b), float32 row-major, on v_mfma_f32_32x32x2_f32.
-//   * Block tile 128 x 128 x 32, 256 threads = 4 waves in 2 x 2, a wave owns 64 x 64 = 2 x 2 MFMA tiles of
-//     32 x 32 (16 accumulator registers each).  Lane l supplies A[i = l & 31][k = l >> 5] and
-//     B[k = l >> 5][j = l & 31]; the result sits at D[row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5)][col = l & 31].
-//   * A tile in LDS row-major with stride 34 floats: the 32 rows x 2 k of one operand read fall on 64
-//     different banks (34 m mod 64 takes every even bank once for m < 32, the second k the odd ones).  B tile
-//     k-major with stride 160: the two k rows of a read are 32 banks apart.  Reads are conflict-free
-//     ds_read_b32; a k step of 2 costs a wave 4 reads for 4 MFMAs of 64 cycles each.
-//   * The next tile's global loads are issued before the MFMAs of the current one (register prefetch,
-//     one LDS buffer, two barriers per tile).
+// Dense layer (bn_dense_kernel): Y = act(A W + b), float32 row-major, on the FP32 tile of gemm_tiles.h (block
+// 128 x 128 x 32 on v_mfma_f32_32x32x2_f32; the tiling, the LDS layout and the prefetch are described there).
 //   * Every output element is ONE chain of fused multiply-adds over k ascending from a zero accumulator
 //     (the MFMA is bit for bit that chain), bias added last, then the activation.  The chain of an element
 //     reads its own A row and W column only: the value does not depend on M, on the row's place in the
@@ -19,25 +11,16 @@
 //     over rows of width gw: the five-frame stack of the second network (gw = 80, gs = 5) is read straight
 //     from the first network's output and never written to memory.
 //
-// bfloat16 dense layer (bn_dense_bf16_kernel): Y = act(bf16(A) bf16(W) + b) on v_mfma_f32_32x32x16_bf16, for the
-// layers that read sigmoid outputs (W2, W3, W6, W7).  A and Y are float32 in memory, the sums float32.
+// bfloat16 dense layer (bn_dense_bf16_kernel): Y = act(bf16(A) bf16(W) + b) on the bfloat16 tile of gemm_tiles.h
+// (block 128 x 128 x 64 on v_mfma_f32_32x32x16_bf16, XCD-contiguous workgroup order), for the layers that read
+// sigmoid outputs (W2, W3, W6, W7).  A and Y are float32 in memory, the sums float32, one chain over all k.
 //   * Weight image (bn_pack_bf16_kernel, once per network): Wt[n][kp] bfloat16, k-contiguous per output column,
-//     kp = K rounded up to the k tile of 64 and zero beyond K.  Lane l of the MFMA holds A[l & 31][8 (l >> 5) + j]
-//     and B[8 (l >> 5) + j][l & 31], j = 0..7: a B fragment is 8 consecutive k of one column, i.e. 16 contiguous
-//     bytes of the image, and an A fragment 8 consecutive k of one row.  No transpose anywhere.
+//     kp = K rounded up to the k tile of 64 and zero beyond K.
 //   * Rounding: to nearest, ties to even, by v_cvt_pk_bf16_f32 (a NaN stays a NaN), for A in the loader before
 //     the LDS write and for W in the pack kernel, so operands that were rounded beforehand give the same bits.
 //     (The same rounding in integer arithmetic, about 7 instructions per element, was measured 10 % slower on the
 //     square layer at 1500.)
-//   * Block tile 128 x 128 x 64, 4 waves in 2 x 2, a wave owns 64 x 64 = 2 x 2 MFMA tiles; a k tile is 4 steps
-//     of 16 and costs a wave 16 ds_read_b128 for 16 MFMAs.  Both tiles sit in LDS as [row][k] with a row stride
-//     of 144 bytes (9 slots of 16): the 16 lanes that a ds_read_b128 serves together read one k chunk of 16 rows
-//     that differ modulo 16, and 9 r mod 16 is a bijection, so they fall on 16 different slots of the 256-byte
-//     bank row; the 8 lanes that a ds_write_b128 serves together write 128 contiguous bytes of one row.
-//   * Next tile prefetched into registers before the MFMAs (8 float4 of A, 4 uint4 of W), one LDS buffer, two
-//     barriers per tile, as bn_dense_kernel.  Tile rows beyond M and columns beyond N repeat the last valid one
-//     (no branch between the loads; rows and columns of a product do not mix and the epilogue stores neither);
-//     k beyond K is zero in both operands, and a zero product leaves a float32 sum as it is.
+//   * A is prefetched as 8 float4 per thread and k tile; tile rows beyond M repeat the last valid one.
 //   * An element's value depends on its A row, its W column and K only (the MFMA's fixed summation order over
 //     the 16 k of a step, steps ascending), not on M, the row's place or the tiling: batch invariance as above.
 //
@@ -58,15 +41,11 @@
 
 #include "snf_internal.h"
 #include "device_fft.h"
+#include "gemm_tiles.h"
 
 namespace snf {
 
 namespace {
-
-constexpr int kBM = 128, kBN = 128, kBK = 32;
-constexpr int kLdA = 34;    // floats per A row in LDS
-constexpr int kLdB = 160;   // floats per B k-row in LDS
-constexpr int kThreads = 256;
 
 struct DenseArgs {
   const float* x;
@@ -82,128 +61,74 @@ struct DenseArgs {
 
 __device__ __forceinline__ float bn_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
-// 4 consecutive k of A row r (source base `row0`), zeros outside K
-__device__ __forceinline__ float4 load_a4(const DenseArgs& g, bool row_ok, int64_t row0, int k) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!row_ok || k >= g.K) return v;
-  if (g.a_row) {
-    if (g.vec_a) {
-      const int blk = k / g.gw, c = k - blk * g.gw;
-      return *reinterpret_cast<const float4*>(g.x + (row0 + static_cast<int64_t>(g.gs) * blk) * g.gw + c);
+// A of the FP32 layer: plain or gathered rows
+struct DenseRows {
+  const DenseArgs& g;
+  int64_t src[4];   // source base row of this thread's four tile rows
+  bool ok[4];
+  __device__ __forceinline__ DenseRows(const DenseArgs& g_, const Tile& t) : g(g_) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t r = t.m0 + t.lr + 32 * i;
+      ok[i] = r < g.M;
+      src[i] = ok[i] ? (g.a_row ? g.a_row[r] : r) : 0;
     }
-    float t[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < 4; ++j) {
-      const int kk = k + j;
-      if (kk < g.K) {
-        const int blk = kk / g.gw, c = kk - blk * g.gw;
-        t[j] = g.x[(row0 + static_cast<int64_t>(g.gs) * blk) * g.gw + c];
-      }
-    }
-    return make_float4(t[0], t[1], t[2], t[3]);
   }
-  const float* p = g.x + row0 * g.K + k;
-  if (g.vec_a) return *reinterpret_cast<const float4*>(p);
-  v.x = p[0];
-  if (k + 1 < g.K) v.y = p[1];
-  if (k + 2 < g.K) v.z = p[2];
-  if (k + 3 < g.K) v.w = p[3];
-  return v;
-}
+  // 4 consecutive k of tile row i, zeros outside M and K
+  __device__ __forceinline__ float4 operator()(int i, int k) const {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!ok[i] || k >= g.K) return v;
+    if (g.a_row) {
+      if (g.vec_a) {
+        const int blk = k / g.gw, c = k - blk * g.gw;
+        return *reinterpret_cast<const float4*>(g.x + (src[i] + static_cast<int64_t>(g.gs) * blk) * g.gw + c);
+      }
+      float t[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int j = 0; j < 4; ++j) {
+        const int kk = k + j;
+        if (kk < g.K) {
+          const int blk = kk / g.gw, c = kk - blk * g.gw;
+          t[j] = g.x[(src[i] + static_cast<int64_t>(g.gs) * blk) * g.gw + c];
+        }
+      }
+      return make_float4(t[0], t[1], t[2], t[3]);
+    }
+    const float* p = g.x + src[i] * g.K + k;
+    if (g.vec_a) return *reinterpret_cast<const float4*>(p);
+    v.x = p[0];
+    if (k + 1 < g.K) v.y = p[1];
+    if (k + 2 < g.K) v.z = p[2];
+    if (k + 3 < g.K) v.w = p[3];
+    return v;
+  }
+};
 
-__device__ __forceinline__ float4 load_b4(const DenseArgs& g, int k, int n) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (k >= g.K || n >= g.N) return v;
-  const float* p = g.w + static_cast<int64_t>(k) * g.N + n;
-  if (g.vec_b) return *reinterpret_cast<const float4*>(p);
-  v.x = p[0];
-  if (n + 1 < g.N) v.y = p[1];
-  if (n + 2 < g.N) v.z = p[2];
-  if (n + 3 < g.N) v.w = p[3];
-  return v;
+// epilogue of both layers: bias, activation, one store per element
+__device__ __forceinline__ void dense_epilogue(const Tile& t, const f32x16 (&acc)[2][2], const float* b, int act,
+                                               float* y, int64_t M, int N) {
+  for_each_owned_pair(t, acc, N, [&](int c) __attribute__((always_inline)) {
+    const float bias = b[c];
+    auto one = [=](int64_t row, float v) __attribute__((always_inline)) {
+      if (row >= M) return;
+      v += bias;
+      if (act) v = bn_sigmoid(v);
+      y[row * N + c] = v;
+    };
+    return [=](int64_t row, float v0, float v1) __attribute__((always_inline)) {
+      one(row, v0);
+      one(row + 1, v1);
+    };
+  });
 }
 
 __global__ void __launch_bounds__(kThreads) bn_dense_kernel(const DenseArgs g, int n_tiles_n) {
-  __shared__ __attribute__((aligned(16))) float As[kBM * kLdA];
-  __shared__ __attribute__((aligned(16))) float Bs[kBK * kLdB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
-  const int64_t m0 = static_cast<int64_t>(blockIdx.x / n_tiles_n) * kBM;
-  const int n0 = static_cast<int>(blockIdx.x % n_tiles_n) * kBN;
-  // loader coordinates
-  const int a_kq = tid & 7, a_m = tid >> 3;     // A: rows a_m + 32 i, columns 4 a_kq ..
-  const int b_nq = tid & 31, b_k = tid >> 5;    // B: k rows b_k + 8 i, columns 4 b_nq ..
-  int64_t a_src[4];
-  bool a_ok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t r = m0 + a_m + 32 * i;
-    a_ok[i] = r < g.M;
-    a_src[i] = a_ok[i] ? (g.a_row ? g.a_row[r] : r) : 0;
-  }
+  const Tile t = tile_of_workgroup<false>(n_tiles_n);
   f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-  float4 ra[4], rb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ra[i] = load_a4(g, a_ok[i], a_src[i], 4 * a_kq);
-    rb[i] = load_b4(g, b_k + 8 * i, n0 + 4 * b_nq);
-  }
-  for (int k0 = 0; k0 < g.K; k0 += kBK) {
-    __syncthreads();   // the previous tile's operand reads are done
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float2* pa = reinterpret_cast<float2*>(As + (a_m + 32 * i) * kLdA + 4 * a_kq);
-      pa[0] = make_float2(ra[i].x, ra[i].y);
-      pa[1] = make_float2(ra[i].z, ra[i].w);
-      *reinterpret_cast<float4*>(Bs + (b_k + 8 * i) * kLdB + 4 * b_nq) = rb[i];
-    }
-    __syncthreads();
-    if (k0 + kBK < g.K) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ra[i] = load_a4(g, a_ok[i], a_src[i], k0 + kBK + 4 * a_kq);
-        rb[i] = load_b4(g, k0 + kBK + b_k + 8 * i, n0 + 4 * b_nq);
-      }
-    }
-    const int kmax = min(kBK, (g.K - k0 + 1) & ~1);
-    const float* pa = As + (wm * 64 + li) * kLdA + lh;
-    const float* pb = Bs + lh * kLdB + wn * 64 + li;
-    for (int kk = 0; kk < kmax; kk += 2) {
-      const float a0 = pa[kk], a1 = pa[32 * kLdA + kk];
-      const float b0 = pb[kk * kLdB], b1 = pb[kk * kLdB + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-  }
-  // epilogue: bias, activation, one store per element
-#pragma unroll
-  for (int tn = 0; tn < 2; ++tn) {
-    const int c = n0 + wn * 64 + tn * 32 + li;
-    if (c >= g.N) continue;
-    const float bias = g.b[c];
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row >= g.M) continue;
-        float v = acc[tm][tn][r] + bias;
-        if (g.act) v = bn_sigmoid(v);
-        g.y[row * g.N + c] = v;
-      }
-    }
-  }
+  gemm_f32<0>(t, DenseRows(g, t), g.w, g.K, g.N, g.vec_b, acc);
+  dense_epilogue(t, acc, g.b, g.act, g.y, g.M, g.N);
 }
 
 // ---- bfloat16 dense layer -------------------------------------------------------------------------------
-// (k tile kQK, LDS row stride kQLd, fragment types and the rounding bf16_rne / bf16_pack2: snf_internal.h)
 struct DenseBf16Args {
   const float* x;
   const uint16_t* wt;   // packed weights Wt[N][Kp]
@@ -213,122 +138,47 @@ struct DenseBf16Args {
   int K, Kp, N, act;
 };
 
-// 4 consecutive k of row `row` (< M) of x, zeros outside K.  kVec (K a multiple of 4, x 16-byte aligned): one
-// unconditional 16-byte load from a clamped address and a select, so that no branch separates the loads of a tile
+// A of the bfloat16 layer: float32 rows, rounded at the LDS write.  kVec (K a multiple of 4, x 16-byte aligned):
+// unconditional 16-byte loads from a clamped address and a select, so that no branch separates the loads of a tile
 template <bool kVec>
-__device__ __forceinline__ float4 load_q4(const DenseBf16Args& g, int64_t row, int k) {
-  if (kVec) {
-    const float4 t = *reinterpret_cast<const float4*>(g.x + row * g.K + min(k, g.K - 4));
-    return k < g.K ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+struct DenseRowsBf16 {
+  struct Frag { float4 lo, hi; };
+  const DenseBf16Args& g;
+  int64_t row[4];   // tile rows beyond M repeat the last one
+  __device__ __forceinline__ DenseRowsBf16(const DenseBf16Args& g_, const Tile& t) : g(g_) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) row[i] = min(t.m0 + t.lr + 32 * i, g.M - 1);
   }
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (k >= g.K) return v;
-  const float* p = g.x + row * g.K + k;
-  v.x = p[0];
-  if (k + 1 < g.K) v.y = p[1];
-  if (k + 2 < g.K) v.z = p[2];
-  if (k + 3 < g.K) v.w = p[3];
-  return v;
-}
-
-// 8 consecutive k of column n (< N) of the packed weights (k < Kp always: the image is padded)
-__device__ __forceinline__ uint4 load_w8(const DenseBf16Args& g, int n, int k) {
-  return *reinterpret_cast<const uint4*>(g.wt + static_cast<int64_t>(n) * g.Kp + k);
-}
+  // 4 consecutive k of row r (< M) of x, zeros outside K
+  __device__ __forceinline__ float4 load_q4(int64_t r, int k) const {
+    if (kVec) {
+      const float4 v = *reinterpret_cast<const float4*>(g.x + r * g.K + min(k, g.K - 4));
+      return k < g.K ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (k >= g.K) return v;
+    const float* p = g.x + r * g.K + k;
+    v.x = p[0];
+    if (k + 1 < g.K) v.y = p[1];
+    if (k + 2 < g.K) v.z = p[2];
+    if (k + 3 < g.K) v.w = p[3];
+    return v;
+  }
+  __device__ __forceinline__ Frag load(int i, int k) const {
+    return Frag{load_q4(row[i], k), load_q4(row[i], k + 4)};
+  }
+  __device__ __forceinline__ u32x4 bits(const Frag& f) const {
+    return u32x4{bf16_pack2(f.lo.x, f.lo.y), bf16_pack2(f.lo.z, f.lo.w), bf16_pack2(f.hi.x, f.hi.y),
+                 bf16_pack2(f.hi.z, f.hi.w)};
+  }
+};
 
 template <bool kVec>
 __global__ void __launch_bounds__(kThreads, 3) bn_dense_bf16_kernel(const DenseBf16Args g, int n_tiles_n) {
-  __shared__ __attribute__((aligned(16))) uint16_t As[kBM * kQLd];
-  __shared__ __attribute__((aligned(16))) uint16_t Bs[kBN * kQLd];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
-  // Workgroups go to the 8 XCDs in turn, each with an L2 of its own: give every XCD a contiguous run of tiles,
-  // so that the tiles_n workgroups that share a block of A rows meet in one L2 (measured + 5 to 8 % on the
-  // square layers at 500 and 1500 against the plain order, same bits).  A bijection of the workgroup ids.
-  const unsigned nwg = gridDim.x, xcd = blockIdx.x % kXcds, q = nwg / kXcds, r = nwg % kXcds;
-  const unsigned id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + blockIdx.x / kXcds;
-  const int64_t m0 = static_cast<int64_t>(id / n_tiles_n) * kBM;
-  const int n0 = static_cast<int>(id % n_tiles_n) * kBN;
-  // loader coordinates, the same for both operands: tile rows l_r + 32 i, k 8 l_c .. 8 l_c + 7
-  const int l_c = tid & 7, l_r = tid >> 3;
-  // tile rows beyond M and columns beyond N repeat the last one: rows and columns of a product do not mix,
-  // and the epilogue stores neither
-  int64_t a_row[4];
-  int b_col[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    a_row[i] = min(m0 + l_r + 32 * i, g.M - 1);
-    b_col[i] = min(n0 + l_r + 32 * i, g.N - 1);
-  }
+  const Tile t = tile_of_workgroup<true>(n_tiles_n);
   f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-  float4 ra[4][2];
-  uint4 rb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ra[i][0] = load_q4<kVec>(g, a_row[i], 8 * l_c);
-    ra[i][1] = load_q4<kVec>(g, a_row[i], 8 * l_c + 4);
-    rb[i] = load_w8(g, b_col[i], 8 * l_c);
-  }
-  const uint16_t* pa = As + (wm * 64 + li) * kQLd + 8 * lh;
-  const uint16_t* pb = Bs + (wn * 64 + li) * kQLd + 8 * lh;
-  for (int k0 = 0; k0 < g.K; k0 += kQK) {
-    __syncthreads();   // the previous tile's operand reads are done
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      uint4 q;
-      q.x = bf16_pack2(ra[i][0].x, ra[i][0].y);
-      q.y = bf16_pack2(ra[i][0].z, ra[i][0].w);
-      q.z = bf16_pack2(ra[i][1].x, ra[i][1].y);
-      q.w = bf16_pack2(ra[i][1].z, ra[i][1].w);
-      *reinterpret_cast<uint4*>(As + (l_r + 32 * i) * kQLd + 8 * l_c) = q;
-      *reinterpret_cast<uint4*>(Bs + (l_r + 32 * i) * kQLd + 8 * l_c) = rb[i];
-    }
-    __syncthreads();
-    if (k0 + kQK < g.K) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ra[i][0] = load_q4<kVec>(g, a_row[i], k0 + kQK + 8 * l_c);
-        ra[i][1] = load_q4<kVec>(g, a_row[i], k0 + kQK + 8 * l_c + 4);
-        rb[i] = load_w8(g, b_col[i], k0 + kQK + 8 * l_c);
-      }
-    }
-    // always the whole tile: beyond K both operands are zeros in LDS, and a zero product leaves a sum as it is
-#pragma unroll
-    for (int s = 0; s < kQK / 16; ++s) {
-      const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(pa + 16 * s);
-      const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(pa + 32 * kQLd + 16 * s);
-      const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(pb + 16 * s);
-      const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(pb + 32 * kQLd + 16 * s);
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
-    }
-  }
-  // epilogue: bias, activation, one store per element (as bn_dense_kernel)
-#pragma unroll
-  for (int tn = 0; tn < 2; ++tn) {
-    const int c = n0 + wn * 64 + tn * 32 + li;
-    if (c >= g.N) continue;
-    const float bias = g.b[c];
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (row >= g.M) continue;
-        float v = acc[tm][tn][r] + bias;
-        if (g.act) v = bn_sigmoid(v);
-        g.y[row * g.N + c] = v;
-      }
-    }
-  }
+  gemm_bf16<0>(t, DenseRowsBf16<kVec>(g, t), g.wt, g.K, g.Kp, g.N, acc);
+  dense_epilogue(t, acc, g.b, g.act, g.y, g.M, g.N);
 }
 
 // wt[n][k] = bfloat16(w[k][n]) for k < K, 0 for K <= k < Kp: 32 x 32 tiles transposed through LDS
@@ -665,11 +515,10 @@ int launch_bn_dense(const float* x, int64_t M, int K, const float* w, const floa
   const bool x16 = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
   g.vec_a = x16 && (a_row ? (gw % 4 == 0 && K % 4 == 0) : K % 4 == 0);
   g.vec_b = (reinterpret_cast<uintptr_t>(w) & 15) == 0 && N % 4 == 0;
-  const int64_t tiles_m = (M + kBM - 1) / kBM;
-  const int tiles_n = (N + kBN - 1) / kBN;
-  if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "dense layer: too many tiles for one launch");
-  hipLaunchKernelGGL(bn_dense_kernel, dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g,
-                     tiles_n);
+  unsigned grid;
+  int tiles_n;
+  if (int rc = gemm_tile_grid(M, N, "dense layer: too many tiles for one launch", &grid, &tiles_n)) return rc;
+  hipLaunchKernelGGL(bn_dense_kernel, dim3(grid), dim3(kThreads), 0, stream, g, tiles_n);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
 }
@@ -690,11 +539,11 @@ int launch_bn_dense_bf16(const float* x, int64_t M, int K, const uint16_t* wt, c
   DenseBf16Args g;
   g.x = x; g.wt = wt; g.b = b; g.y = y; g.M = M; g.K = K; g.Kp = bn_bf16_padded_k(K); g.N = N; g.act = act;
   const bool vec = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && K % 4 == 0;
-  const int64_t tiles_m = (M + kBM - 1) / kBM;
-  const int tiles_n = (N + kBN - 1) / kBN;
-  if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "dense layer: too many tiles for one launch");
-  hipLaunchKernelGGL(vec ? bn_dense_bf16_kernel<true> : bn_dense_bf16_kernel<false>,
-                     dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g, tiles_n);
+  unsigned grid;
+  int tiles_n;
+  if (int rc = gemm_tile_grid(M, N, "dense layer: too many tiles for one launch", &grid, &tiles_n)) return rc;
+  hipLaunchKernelGGL(vec ? bn_dense_bf16_kernel<true> : bn_dense_bf16_kernel<false>, dim3(grid), dim3(kThreads), 0,
+                     stream, g, tiles_n);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
 }

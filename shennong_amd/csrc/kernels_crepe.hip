@@ -1,9 +1,8 @@
 // CREPE pitch tracker (Kim et al., ICASSP 2018; reference processor/pitch_crepe.py): frame ingest, the six
 // convolution blocks and the classifier on the FP32 matrix cores, and the decoders.
 //
-// Convolution (crepe_conv_kernel): an implicit GEMM Y = epilogue(A W), the tiling of bn_dense_kernel
-// (kernels_bottleneck.hip: block 128 x 128 x 32, 4 waves of 2 x 2 tiles of v_mfma_f32_32x32x2_f32, LDS strides
-// 34 / 160, register prefetch of the next k tile).
+// Convolution (crepe_conv_kernel): an implicit GEMM Y = epilogue(A W) on the FP32 tile of gemm_tiles.h (block
+// 128 x 128 x 32 on v_mfma_f32_32x32x2_f32; the tiling, the LDS layout and the prefetch are described there).
 //   * Activations are channels-last, [frame][position][channel].  Output row r = (frame f, position t) of a
 //     layer with T positions reads ONE contiguous run of K = width * C_in floats of its frame's block of L
 //     floats, from s = (t * stride - pad_left) * C_in on; what falls outside [0, L) is the zero padding.  The A
@@ -25,9 +24,8 @@
 //     round-off (about sqrt(K) eps times the running sum) was 19.5 times that of float32 numpy on the host.
 //
 // bfloat16 convolution (crepe_conv_bf16_kernel, blocks 2 to 6 under precision 'bfloat16'): the same implicit
-// GEMM on v_mfma_f32_32x32x16_bf16, with the tile of bn_dense_bf16_kernel (kernels_bottleneck.hip: block
-// 128 x 128 x 64, 4 waves of 2 x 2 MFMA tiles, both LDS tiles [row][k] at a row stride of 144 bytes, ds_read_b128
-// fragments, register prefetch of the next k tile, XCD-contiguous workgroup order).
+// GEMM on the bfloat16 tile of gemm_tiles.h (block 128 x 128 x 64 on v_mfma_f32_32x32x16_bf16, XCD-contiguous
+// workgroup order).
 //   * W is the packed image Wt[N][Kp] of bn_pack_bf16_kernel: a B fragment is 16 contiguous bytes.
 //   * A is the gather above, 8 consecutive k per load.  C_in is a multiple of 8, so s, k, L and K are too and
 //     a fragment lies inside the frame's block as a whole or not at all: one 16-byte load of bfloat16 or two of
@@ -51,16 +49,14 @@
 
 #include "snf_internal.h"
 #include "device_fft.h"
+#include "gemm_tiles.h"
 
 namespace snf {
 
 namespace {
 
-constexpr int kBM = 128, kBN = 128, kBK = 32;
-constexpr int kLdA = 34;    // floats per A row in LDS
-constexpr int kLdB = 160;   // floats per B k-row in LDS
-constexpr int kThreads = 256;
-constexpr int kChain = 256;   // k per multiply-add chain (a multiple of kBK)
+constexpr int kChain = 256;      // k per multiply-add chain of the FP32 kernel (a multiple of kBK)
+constexpr int kChainBf = 1024;   // ... of the bfloat16 kernel (a multiple of kQK)
 
 constexpr int kFrame = 1024, kHalf = 512, kBinsOut = 360, kBand = 11, kBandW = 2 * kBand + 1;
 // float64 offsets in the decoder's table blob
@@ -86,151 +82,84 @@ struct ConvArgs {
 
 __device__ __forceinline__ float crepe_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
-// 4 consecutive k of the row whose run starts `s` floats into the frame block at `base`; zeros outside
-__device__ __forceinline__ float4 load_a4(const ConvArgs& g, bool row_ok, int64_t base, int s, int k) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!row_ok || k >= g.K) return v;
-  const int p = s + k;
-  if (g.vec_a) {   // s, k, L and K are multiples of 4: the four floats are inside together or not at all
-    if (p < 0 || p >= g.L) return v;
-    return *reinterpret_cast<const float4*>(g.x + base + p);
-  }
-  float t[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (k + j < g.K && p + j >= 0 && p + j < g.L) t[j] = g.x[base + p + j];
-  return make_float4(t[0], t[1], t[2], t[3]);
+// The run of a tile row: row r = (frame f, position t) reads from s = t * step - lead on inside the frame's block
+template <class Args>
+__device__ __forceinline__ void conv_run(const Args& g, int64_t r, int64_t* base, int* s) {
+  const int64_t f = r / g.T;
+  *base = f * g.L;
+  *s = static_cast<int>(r - f * g.T) * g.step - g.lead;
 }
 
-__device__ __forceinline__ float4 load_b4(const ConvArgs& g, int k, int n) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (k >= g.K || n >= g.N) return v;
-  const float* p = g.w + static_cast<int64_t>(k) * g.N + n;
-  if (g.vec_b) return *reinterpret_cast<const float4*>(p);
-  v.x = p[0];
-  if (n + 1 < g.N) v.y = p[1];
-  if (n + 2 < g.N) v.z = p[2];
-  if (n + 3 < g.N) v.w = p[3];
-  return v;
+// A of the FP32 convolution
+struct ConvRuns {
+  const ConvArgs& g;
+  int64_t base[4];
+  int s[4];
+  bool ok[4];
+  __device__ __forceinline__ ConvRuns(const ConvArgs& g_, const Tile& t) : g(g_) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t r = t.m0 + t.lr + 32 * i;
+      ok[i] = r < g.M;
+      base[i] = 0;
+      s[i] = -g.lead;
+      if (ok[i]) conv_run(g, r, &base[i], &s[i]);
+    }
+  }
+  // 4 consecutive k of tile row i; zeros outside the block, M and K
+  __device__ __forceinline__ float4 operator()(int i, int k) const {
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!ok[i] || k >= g.K) return v;
+    const int p = s[i] + k;
+    if (g.vec_a) {   // s, k, L and K are multiples of 4: the four floats are inside together or not at all
+      if (p < 0 || p >= g.L) return v;
+      return *reinterpret_cast<const float4*>(g.x + base[i] + p);
+    }
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (k + j < g.K && p + j >= 0 && p + j < g.L) t[j] = g.x[base[i] + p + j];
+    return make_float4(t[0], t[1], t[2], t[3]);
+  }
+};
+
+// epilogue of both kernels: bias, ReLU and normalisation or sigmoid, the pool over the row pair, one
+// store(index, value) per output
+template <class Args, class Store>
+__device__ __forceinline__ void conv_epilogue(const Args& g, const Tile& t, const f32x16 (&sum)[2][2], Store&& store) {
+  const bool norm = g.flags & kConvNorm, pool = g.flags & kConvPool, sigm = g.flags & kConvSigmoid;
+  for_each_owned_pair(t, sum, g.N, [&](int c) __attribute__((always_inline)) {
+    const float bias = g.b[c];
+    const float sc = norm ? g.scale[c] : 1.0f, sh = norm ? g.shift[c] : 0.0f;
+    return [=, &g, &store](int64_t row, float v0, float v1) __attribute__((always_inline)) {
+      v0 += bias;
+      v1 += bias;
+      if (norm) {
+        v0 = fmaf(fmaxf(v0, 0.0f), sc, sh);
+        v1 = fmaf(fmaxf(v1, 0.0f), sc, sh);
+      }
+      if (sigm) {
+        v0 = crepe_sigmoid(v0);
+        v1 = crepe_sigmoid(v1);
+      }
+      if (pool) {   // (M is even: the pair is inside together)
+        if (row < g.M) store((row >> 1) * g.N + c, fmaxf(v0, v1));
+      } else {
+        if (row < g.M) store(row * g.N + c, v0);
+        if (row + 1 < g.M) store((row + 1) * g.N + c, v1);
+      }
+    };
+  });
 }
 
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2))) crepe_conv_kernel(const ConvArgs g, int n_tiles_n) {
-  __shared__ __attribute__((aligned(16))) float As[kBM * kLdA];
-  __shared__ __attribute__((aligned(16))) float Bs[kBK * kLdB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
-  const int64_t m0 = static_cast<int64_t>(blockIdx.x / n_tiles_n) * kBM;
-  const int n0 = static_cast<int>(blockIdx.x % n_tiles_n) * kBN;
-  const int a_kq = tid & 7, a_m = tid >> 3;     // A: rows a_m + 32 i, columns 4 a_kq ..
-  const int b_nq = tid & 31, b_k = tid >> 5;    // B: k rows b_k + 8 i, columns 4 b_nq ..
-  int64_t a_base[4];
-  int a_s[4];
-  bool a_ok[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t r = m0 + a_m + 32 * i;
-    a_ok[i] = r < g.M;
-    const int64_t f = a_ok[i] ? r / g.T : 0;
-    const int t = a_ok[i] ? static_cast<int>(r - f * g.T) : 0;
-    a_base[i] = f * g.L;
-    a_s[i] = t * g.step - g.lead;
-  }
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-  f32x16 sum[2][2];   // the partial sums of the k blocks done so far, added in ascending order
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sum[a][b][r] = 0.0f;
-  float4 ra[4], rb[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ra[i] = load_a4(g, a_ok[i], a_base[i], a_s[i], 4 * a_kq);
-    rb[i] = load_b4(g, b_k + 8 * i, n0 + 4 * b_nq);
-  }
-  for (int k0 = 0; k0 < g.K; k0 += kBK) {
-    __syncthreads();   // the previous tile's operand reads are done
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      float2* pa = reinterpret_cast<float2*>(As + (a_m + 32 * i) * kLdA + 4 * a_kq);
-      pa[0] = make_float2(ra[i].x, ra[i].y);
-      pa[1] = make_float2(ra[i].z, ra[i].w);
-      *reinterpret_cast<float4*>(Bs + (b_k + 8 * i) * kLdB + 4 * b_nq) = rb[i];
-    }
-    __syncthreads();
-    if (k0 + kBK < g.K) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        ra[i] = load_a4(g, a_ok[i], a_base[i], a_s[i], k0 + kBK + 4 * a_kq);
-        rb[i] = load_b4(g, k0 + kBK + b_k + 8 * i, n0 + 4 * b_nq);
-      }
-    }
-    const int kmax = min(kBK, (g.K - k0 + 1) & ~1);
-    const float* pa = As + (wm * 64 + li) * kLdA + lh;
-    const float* pb = Bs + lh * kLdB + wn * 64 + li;
-    for (int kk = 0; kk < kmax; kk += 2) {
-      const float a0 = pa[kk], a1 = pa[32 * kLdA + kk];
-      const float b0 = pb[kk * kLdB], b1 = pb[kk * kLdB + 32];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
-    if ((k0 + kBK) % kChain == 0 || k0 + kBK >= g.K) {   // a chain of kChain k is complete (or K is)
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            sum[a][b][r] += acc[a][b][r];
-            acc[a][b][r] = 0.0f;
-          }
-    }
-  }
-  // epilogue: bias, ReLU and normalisation or sigmoid, the pool over the row pair, one store per output
-  const bool norm = g.flags & kConvNorm, pool = g.flags & kConvPool, sigm = g.flags & kConvSigmoid;
-#pragma unroll
-  for (int tn = 0; tn < 2; ++tn) {
-    const int c = n0 + wn * 64 + tn * 32 + li;
-    if (c >= g.N) continue;
-    const float bias = g.b[c];
-    const float sc = norm ? g.scale[c] : 1.0f, sh = norm ? g.shift[c] : 0.0f;
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) {
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const int64_t row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;   // even; r + 1 is row + 1
-        float v0 = sum[tm][tn][r] + bias, v1 = sum[tm][tn][r + 1] + bias;
-        if (norm) {
-          v0 = fmaf(fmaxf(v0, 0.0f), sc, sh);
-          v1 = fmaf(fmaxf(v1, 0.0f), sc, sh);
-        }
-        if (sigm) {
-          v0 = crepe_sigmoid(v0);
-          v1 = crepe_sigmoid(v1);
-        }
-        if (pool) {   // (M is even: the pair is inside together)
-          if (row < g.M) g.y[(row >> 1) * g.N + c] = fmaxf(v0, v1);
-        } else {
-          if (row < g.M) g.y[row * g.N + c] = v0;
-          if (row + 1 < g.M) g.y[(row + 1) * g.N + c] = v1;
-        }
-      }
-    }
-  }
+  const Tile t = tile_of_workgroup<false>(n_tiles_n);
+  f32x16 sum[2][2];
+  gemm_f32<kChain>(t, ConvRuns(g, t), g.w, g.K, g.N, g.vec_b, sum);
+  conv_epilogue(g, t, sum, [&](int64_t at, float v) __attribute__((always_inline)) { g.y[at] = v; });
 }
 
 // ---- bfloat16 convolution -------------------------------------------------------------------------------
-constexpr int kChainBf = 1024;   // k per chain of the bfloat16 kernel (a multiple of kQK)
-
 struct ConvBf16Args {
   const void* x;        // float32 or bfloat16 (the template parameter)
   const uint16_t* wt;   // packed kernel Wt[N][Kp]
@@ -242,12 +171,12 @@ struct ConvBf16Args {
   int K, Kp, N, T, step, lead, L, flags, y_bf16;
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // 8 bfloat16, 16 bytes
-
-// 8 consecutive k of a row, as the loader keeps them until the LDS write
+// 8 consecutive k of a row, as the loader keeps them until the LDS write; `in`: the run lies inside [0, L) and
+// below K, else the LDS write puts zeros
 template <bool kSrcBf16>
 struct Frag8 {
   float4 lo, hi;
+  bool in;
   __device__ __forceinline__ u32x4 bits() const {
     return u32x4{bf16_pack2(lo.x, lo.y), bf16_pack2(lo.z, lo.w), bf16_pack2(hi.x, hi.y), bf16_pack2(hi.z, hi.w)};
   }
@@ -255,154 +184,50 @@ struct Frag8 {
 template <>
 struct Frag8<true> {
   u32x4 q;
+  bool in;
   __device__ __forceinline__ u32x4 bits() const { return q; }
 };
 
-// k .. k + 7 of the row whose run starts `s` elements into the frame block at `base`, read whole from an address
-// clamped into the block (everything is a multiple of 8); `in`: the run lies inside [0, L) and below K, else
-// the LDS write puts zeros.  The select waits until then, so no branch comes between the loads of a tile.
+// A of the bfloat16 convolution.  Tile rows beyond M repeat the last one.
 template <bool kSrcBf16>
-__device__ __forceinline__ Frag8<kSrcBf16> load_a8(const ConvBf16Args& g, int64_t base, int s, int k, bool* in) {
-  const int p = s + k;
-  *in = k < g.K && p >= 0 && p < g.L;
-  const int64_t at = base + min(max(p, 0), g.L - 8);
-  Frag8<kSrcBf16> f;
-  if constexpr (kSrcBf16) {
-    f.q = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(g.x) + at);
-  } else {
-    const float4* src = reinterpret_cast<const float4*>(static_cast<const float*>(g.x) + at);
-    f.lo = src[0];
-    f.hi = src[1];
+struct ConvRunsBf16 {
+  typedef Frag8<kSrcBf16> Frag;
+  const ConvBf16Args& g;
+  int64_t base[4];
+  int s[4];
+  __device__ __forceinline__ ConvRunsBf16(const ConvBf16Args& g_, const Tile& t) : g(g_) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) conv_run(g, min(t.m0 + t.lr + 32 * i, g.M - 1), &base[i], &s[i]);
   }
-  return f;
-}
+  // k .. k + 7 of tile row i, read whole from an address clamped into the block (everything is a multiple of 8).
+  // The select waits until the LDS write, so no branch comes between the loads of a tile.
+  __device__ __forceinline__ Frag load(int i, int k) const {
+    const int p = s[i] + k;
+    const int64_t at = base[i] + min(max(p, 0), g.L - 8);
+    Frag f;
+    f.in = k < g.K && p >= 0 && p < g.L;
+    if constexpr (kSrcBf16) {
+      f.q = *reinterpret_cast<const u32x4*>(static_cast<const uint16_t*>(g.x) + at);
+    } else {
+      const float4* src = reinterpret_cast<const float4*>(static_cast<const float*>(g.x) + at);
+      f.lo = src[0];
+      f.hi = src[1];
+    }
+    return f;
+  }
+  __device__ __forceinline__ u32x4 bits(const Frag& f) const { return f.in ? f.bits() : u32x4{0u, 0u, 0u, 0u}; }
+};
 
 template <bool kSrcBf16>
 __global__ void __launch_bounds__(kThreads, 2) crepe_conv_bf16_kernel(const ConvBf16Args g, int n_tiles_n) {
-  __shared__ __attribute__((aligned(16))) uint16_t As[kBM * kQLd];
-  __shared__ __attribute__((aligned(16))) uint16_t Bs[kBN * kQLd];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, lh = lane >> 5;
-  // every XCD takes a contiguous run of tiles (bn_dense_bf16_kernel): a bijection of the workgroup ids
-  const unsigned nwg = gridDim.x, xcd = blockIdx.x % kXcds, q = nwg / kXcds, rem = nwg % kXcds;
-  const unsigned id = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + blockIdx.x / kXcds;
-  const int64_t m0 = static_cast<int64_t>(id / n_tiles_n) * kBM;
-  const int n0 = static_cast<int>(id % n_tiles_n) * kBN;
-  // loader coordinates, the same for both operands: tile rows l_r + 32 i, k 8 l_c .. 8 l_c + 7.  Tile rows
-  // beyond M and columns beyond N repeat the last one: the epilogue stores neither.
-  const int l_c = tid & 7, l_r = tid >> 3;
-  int64_t a_base[4];
-  int a_s[4], b_col[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int64_t r = min(m0 + l_r + 32 * i, g.M - 1);
-    const int64_t f = r / g.T;
-    a_base[i] = f * g.L;
-    a_s[i] = static_cast<int>(r - f * g.T) * g.step - g.lead;
-    b_col[i] = min(n0 + l_r + 32 * i, g.N - 1);
-  }
-  f32x16 acc[2][2], sum[2][2];   // the running chain; the chains done so far, added in ascending order
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sum[a][b][r] = 0.0f;
-  Frag8<kSrcBf16> ra[4];
-  u32x4 rb[4];
-  bool a_in[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    ra[i] = load_a8<kSrcBf16>(g, a_base[i], a_s[i], 8 * l_c, &a_in[i]);
-    rb[i] = *reinterpret_cast<const u32x4*>(g.wt + static_cast<int64_t>(b_col[i]) * g.Kp + 8 * l_c);
-  }
-  const uint16_t* pa = As + (wm * 64 + li) * kQLd + 8 * lh;
-  const uint16_t* pb = Bs + (wn * 64 + li) * kQLd + 8 * lh;
-  for (int kc = 0; kc < g.K; kc += kChainBf) {   // one chain: from a zero accumulator, then into the sum
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.0f;
-    const int kend = min(kc + kChainBf, g.K);
-    for (int k0 = kc; k0 < kend; k0 += kQK) {
-      __syncthreads();   // the previous tile's operand reads are done
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        *reinterpret_cast<u32x4*>(As + (l_r + 32 * i) * kQLd + 8 * l_c) = a_in[i] ? ra[i].bits() : u32x4{0u, 0u, 0u, 0u};
-        *reinterpret_cast<u32x4*>(Bs + (l_r + 32 * i) * kQLd + 8 * l_c) = rb[i];
-      }
-      __syncthreads();
-      if (k0 + kQK < g.K) {   // (the image is padded to Kp: the whole tile is there)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          ra[i] = load_a8<kSrcBf16>(g, a_base[i], a_s[i], k0 + kQK + 8 * l_c, &a_in[i]);
-          rb[i] = *reinterpret_cast<const u32x4*>(g.wt + static_cast<int64_t>(b_col[i]) * g.Kp + k0 + kQK + 8 * l_c);
-        }
-      }
-      // always the whole tile: beyond K both operands are zeros in LDS, and a zero product leaves a sum as it is
-#pragma unroll
-      for (int s = 0; s < kQK / 16; ++s) {
-        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(pa + 16 * s);
-        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(pa + 32 * kQLd + 16 * s);
-        const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(pb + 16 * s);
-        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(pb + 32 * kQLd + 16 * s);
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) sum[a][b] += acc[a][b];
-  }
-  // epilogue as crepe_conv_kernel: bias, ReLU and normalisation or sigmoid, the pool over the
-  // row pair, one store per output in the output's type
-  const bool norm = g.flags & kConvNorm, pool = g.flags & kConvPool, sigm = g.flags & kConvSigmoid;
-  float* yf = static_cast<float*>(g.y);
-  uint16_t* yh = static_cast<uint16_t*>(g.y);
-#pragma unroll
-  for (int tn = 0; tn < 2; ++tn) {
-    const int c = n0 + wn * 64 + tn * 32 + li;
-    if (c >= g.N) continue;
-    const float bias = g.b[c];
-    const float sc = norm ? g.scale[c] : 1.0f, sh = norm ? g.shift[c] : 0.0f;
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) {
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const int64_t row = m0 + wm * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;   // even; r + 1 is row + 1
-        float v0 = sum[tm][tn][r] + bias, v1 = sum[tm][tn][r + 1] + bias;
-        if (norm) {
-          v0 = fmaf(fmaxf(v0, 0.0f), sc, sh);
-          v1 = fmaf(fmaxf(v1, 0.0f), sc, sh);
-        }
-        if (sigm) {
-          v0 = crepe_sigmoid(v0);
-          v1 = crepe_sigmoid(v1);
-        }
-        if (pool) {   // (M is even: the pair is inside together)
-          v0 = fmaxf(v0, v1);
-          if (row < g.M) {
-            if (g.y_bf16) yh[(row >> 1) * g.N + c] = bf16_rne(v0);
-            else yf[(row >> 1) * g.N + c] = v0;
-          }
-        } else {
-          if (row < g.M) {
-            if (g.y_bf16) yh[row * g.N + c] = bf16_rne(v0);
-            else yf[row * g.N + c] = v0;
-          }
-          if (row + 1 < g.M) {
-            if (g.y_bf16) yh[(row + 1) * g.N + c] = bf16_rne(v1);
-            else yf[(row + 1) * g.N + c] = v1;
-          }
-        }
-      }
-    }
-  }
+  const Tile t = tile_of_workgroup<true>(n_tiles_n);
+  f32x16 sum[2][2];
+  gemm_bf16<kChainBf>(t, ConvRunsBf16<kSrcBf16>(g, t), g.wt, g.K, g.Kp, g.N, sum);
+  // the store is in the output's type
+  conv_epilogue(g, t, sum, [&](int64_t at, float v) __attribute__((always_inline)) {
+    if (g.y_bf16) static_cast<uint16_t*>(g.y)[at] = bf16_rne(v);
+    else static_cast<float*>(g.y)[at] = v;
+  });
 }
 
 // ---- ingest ---------------------------------------------------------------------------------------------
@@ -564,11 +389,10 @@ int launch_crepe_conv(const float* x, int64_t frames, int T, int step, int lead,
   g.M = frames * T; g.K = K; g.N = N; g.T = T; g.step = step; g.lead = lead; g.L = L; g.flags = flags;
   g.vec_a = (reinterpret_cast<uintptr_t>(x) & 15) == 0 && K % 4 == 0 && L % 4 == 0 && step % 4 == 0 && lead % 4 == 0;
   g.vec_b = (reinterpret_cast<uintptr_t>(w) & 15) == 0 && N % 4 == 0;
-  const int64_t tiles_m = (g.M + kBM - 1) / kBM;
-  const int tiles_n = (N + kBN - 1) / kBN;
-  if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "crepe: too many tiles for one launch");
-  hipLaunchKernelGGL(crepe_conv_kernel, dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g,
-                     tiles_n);
+  unsigned grid;
+  int tiles_n;
+  if (int rc = gemm_tile_grid(g.M, N, "crepe: too many tiles for one launch", &grid, &tiles_n)) return rc;
+  hipLaunchKernelGGL(crepe_conv_kernel, dim3(grid), dim3(kThreads), 0, stream, g, tiles_n);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
 }
@@ -583,11 +407,11 @@ int launch_crepe_conv_bf16(const void* x, int x_bf16, int64_t frames, int T, int
   g.x = x; g.wt = wt; g.b = b; g.scale = scale; g.shift = shift; g.y = y;
   g.M = frames * T; g.K = K; g.Kp = bn_bf16_padded_k(K); g.N = N; g.T = T; g.step = step; g.lead = lead; g.L = L;
   g.flags = flags; g.y_bf16 = y_bf16;
-  const int64_t tiles_m = (g.M + kBM - 1) / kBM;
-  const int tiles_n = (N + kBN - 1) / kBN;
-  if (tiles_m * tiles_n > 0x7FFFFFFFll) return set_error(SNF_E_INVALID, "crepe: too many tiles for one launch");
-  hipLaunchKernelGGL(x_bf16 ? crepe_conv_bf16_kernel<true> : crepe_conv_bf16_kernel<false>,
-                     dim3(static_cast<unsigned>(tiles_m * tiles_n)), dim3(kThreads), 0, stream, g, tiles_n);
+  unsigned grid;
+  int tiles_n;
+  if (int rc = gemm_tile_grid(g.M, N, "crepe: too many tiles for one launch", &grid, &tiles_n)) return rc;
+  hipLaunchKernelGGL(x_bf16 ? crepe_conv_bf16_kernel<true> : crepe_conv_bf16_kernel<false>, dim3(grid), dim3(kThreads),
+                     0, stream, g, tiles_n);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
 }

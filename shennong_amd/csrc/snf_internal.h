@@ -175,6 +175,16 @@ __device__ __forceinline__ uint64_t wave_noise_id(const BatchArgs& b, int64_t u,
   const int64_t n = b.sample_offsets[u + 1] - b.sample_offsets[u];
   return frame_noise_id(local_frame, n, b.utt_noise[u]);
 }
+// Vector types of the matrix-core kernels (gemm_tiles.h, dtw_tiles.h) and the one rounding to bfloat16, which the
+// collate kernels use too (v_cvt_pk_bf16_f32: to nearest, ties to even, subnormals kept, a NaN stays a NaN)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint16_t bf16_rne(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
+__device__ __forceinline__ uint32_t bf16_pack2(float lo, float hi) {
+  f32x2 v = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
 #endif
 
 struct PlpParams {
@@ -510,22 +520,6 @@ int launch_bn_pack_bf16(const float* w, int K, int N, uint16_t* wt, hipStream_t 
 // y = act(bf16(x) bf16(w) + b), float32 accumulation, float32 y
 int launch_bn_dense_bf16(const float* x, int64_t M, int K, const uint16_t* wt, const float* b, int N, int act,
                          float* y, hipStream_t stream);
-#if defined(__HIPCC__)
-// the bfloat16 tile that bn_dense_bf16_kernel and crepe_conv_bf16_kernel share: k tile, LDS row stride, fragment
-// types and the one rounding (v_cvt_pk_bf16_f32: to nearest, ties to even, subnormals kept, a NaN stays a NaN)
-constexpr int kQK = 64;     // k tile: the weight image pads K to a multiple of it
-constexpr int kQLd = 72;    // bfloat16 per tile row in LDS (144 bytes = 9 slots of 16)
-constexpr unsigned kXcds = 8;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ uint16_t bf16_rne(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
-__device__ __forceinline__ uint32_t bf16_pack2(float lo, float hi) {
-  f32x2 v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
-}
-#endif
 int launch_bn_row_map(const int64_t* in_off, const int64_t* out_off, int64_t n_utts, int64_t rows, int64_t* a_row,
                       hipStream_t stream);
 int launch_bn_fbank(const int16_t* wave, const int64_t* soff, const int64_t* foff, int64_t n_utts,
