@@ -87,7 +87,7 @@ static float vecsum(const float* a, int n) {
 /* Summation orders of the pitch tracker.  Kaldi hands these sums to BLAS (cblas_sdot / sgemv), whose
  * order and use of fused multiply-adds depend on the library build, so NO order is "the" Kaldi one;
  * the oracle fixes one that a 16-lane group of a GPU wavefront reproduces bit for bit, and the HIP
- * kernels (csrc/kernels_pitch.hip) implement exactly the same:
+ * kernels (csrc/kernels_pitch_front.hip and its siblings) implement exactly the same:
  *   - chain_dot:  s = fmaf(a[i], b[i], s) for i ascending, from 0 (lag correlations, FIR taps)
  *   - tree16:     16 partial sums p[0..15] added as a balanced binary tree of neighbours
  *                 ((p0+p1)+(p2+p3)) + ((p4+p5)+(p6+p7)) ... (frame mean, frame energy, norm average),

@@ -1,7 +1,7 @@
 // General, batched LinearResample on gfx950: Kaldi's ResampleWaveform (resample.cc LinearResample with a cutoff
 // of 0.99 x half the lower rate and 6 zero crossings), which is what torchaudio's kaldi.resample_waveform
 // computes, for any pair of different rates, down or up, on int16 or float32 samples.  A sibling of
-// pitch_resample_kernel (kernels_pitch.hip), which runs the one pair and sample type the pitch tracker needs.
+// pitch_resample_kernel (kernels_pitch_front.hip), which runs the one pair and sample type the pitch tracker needs.
 //
 // linear_resample_kernel: blockIdx.y = utterance, blockIdx.x = a run of kResampleChunks x kResampleChunk = 1024
 // consecutive outputs of it.  Per chunk of 256 outputs the workgroup stages the input span they touch (at most

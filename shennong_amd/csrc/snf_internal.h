@@ -379,6 +379,14 @@ struct PitchScratch {
 // traceback + POV output
 int launch_pitch(const PitchDevTables& t, const PitchBatch& b, const PitchScratch& w, float* out,
                  hipStream_t stream);
+// its pieces (kernels_pitch_front.hip, kernels_pitch_flat.hip), called by launch_pitch alone.  `trace`: the
+// SNF_PITCH_TRACE knob - pitch_stage_done waits for the stage, reports it and returns nonzero if the call ends
+// behind it; *stop: it ended inside the front stages
+int pitch_stage_done(int trace, const char* name, int index, hipStream_t stream);
+int launch_pitch_front(const PitchDevTables& t, const PitchBatch& b, const PitchScratch& w, int trace,
+                       hipStream_t stream, bool* stop);
+int launch_pitch_viterbi_flat(const PitchDevTables& t, const PitchBatch& b, const PitchScratch& w, size_t lds,
+                              float* out, hipStream_t stream);
 
 int launch_vad(const snf_vad_options& o, const float* in, int in_cols, const int64_t* frame_offsets,
                int64_t n_utts, int64_t total_frames, float* thr_scratch, float* out,

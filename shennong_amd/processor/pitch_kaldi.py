@@ -2,7 +2,7 @@
 
 Same parameters, defaults, outputs and error messages as reference
 shennong/processor/pitch_kaldi.py:73-540; the tracker (NCCF batched-lag correlation + Viterbi per
-utterance, csrc/kernels_pitch.hip) and the post-processing run on the HIP backend (plan kinds PITCH
+utterance, csrc/kernels_pitch_front.hip and csrc/kernels_pitch_viterbi.hip) and the post-processing run on the HIP backend (plan kinds PITCH
 and PITCH_POST).
 """
 

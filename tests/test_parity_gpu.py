@@ -199,7 +199,7 @@ def _pitch_close(got, want):
 @pytest.fixture(params=[1, 2, 4])
 def vit_team(request, monkeypatch):
     """every form of the Viterbi kernel: one wave per utterance (what large batches run on), or a team of two /
-    four waves per utterance (small batches; kernels_pitch.hip viterbi_forward_team) - all bit-identical"""
+    four waves per utterance (small batches; kernels_pitch_viterbi.hip viterbi_forward_team) - all bit-identical"""
     monkeypatch.setenv('SNF_PITCH_TEAM', str(request.param))
     return request.param
 
@@ -248,7 +248,7 @@ def test_pitch_negative_penalty_is_refused(gpu, audio):
     dict(min_f0=70, max_f0=300, delta_pitch=0.01, lowpass_cutoff=800, resample_freq=3200),
 ])
 def test_pitch_option_paths(gpu, synth_waves, opts, vit_team):
-    """option sets that leave the instantiations the default configuration runs on (kernels_pitch.hip:
+    """option sets that leave the instantiations the default configuration runs on (kernels_pitch_viterbi.hip:
     viterbi_forward<7> / <8> / <0>, the overlaid NCCF, the straight-line 12-lag resampling)"""
     proc = KaldiPitchProcessor(**opts)
     waves = list(synth_waves)[:3]
@@ -1261,7 +1261,7 @@ def test_large_batches_and_pinned_utterances(gpu, wav_file):
 
 
 def test_pitch_flat_search(gpu, monkeypatch):
-    """the lane-per-candidate Viterbi search (csrc/kernels_pitch.hip 4c, the default for large batches since round
+    """the lane-per-candidate Viterbi search (csrc/kernels_pitch_flat.hip, the default for large batches since round
     5) returns the bits of the lane-per-state search (SNF_PITCH_FLAT=0) and of the oracle: ragged utterances, some
     short enough for RecomputeBacktraces, digital silence (every cost ties) and noise"""
     monkeypatch.setenv('SNF_PITCH_TEAM', '1')      # one wave per utterance whatever the batch size

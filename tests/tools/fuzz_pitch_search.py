@@ -1,5 +1,5 @@
-"""Randomised differential test of the two Viterbi searches of the pitch tracker (csrc/kernels_pitch.hip:
-section 4, a lane per state, and section 4c, a lane per candidate - the default for large batches since round
+"""Randomised differential test of the two Viterbi searches of the pitch tracker (csrc/kernels_pitch_viterbi.hip,
+a lane per state, and csrc/kernels_pitch_flat.hip, a lane per candidate - the default for large batches since round
 5): random tracker options (hence random numbers of states, penalties and lag tables) and ragged utterances,
 one wave per utterance forced, and the two forms must return the same BITS; one utterance per case is also
 compared with the CPU oracle.  Needs a GPU.

@@ -1,6 +1,6 @@
 """Replay of the Viterbi search of the pitch tracker on the CPU (round 5): for real forward-cost rows (the CPU
 oracle gives the resampled NCCF, the exact argmin is brute force in float32), how many candidates every level of
-csrc/kernels_pitch.hip evaluates, how many scan iterations its lane-per-state passes need and how many long
+csrc/kernels_pitch_viterbi.hip evaluates, how many scan iterations its lane-per-state passes need and how many long
 windows go to the 8-lane teams.  DESIGN.md 4.5 quotes its output.   python tools/pitch_search_replay.py [utterances]"""
 import sys, numpy as np
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
