@@ -781,6 +781,54 @@ int snf_dtw_search(int device_id, const float* d_rows, int32_t dim, const int64_
                    int32_t* d_start, int32_t* d_end, const int64_t* h_curve_first, float* d_curve_cost,
                    int32_t* d_curve_len, int32_t* d_curve_start, void* stream);
 
+/* ---- Search: several non-overlapping detections per pair, and the best few per query ---------------------------
+ * Extensions with no reference call behind them, on top of snf_dtw_search: every place a query occurs in a target,
+ * not only the best one, picked on the device from the ends of the same lattice, so that a search over a corpus
+ * downloads detections and not 12 bytes per target frame.  The definition is this project's own (DESIGN 4.18,
+ * tests/dtw_detect_f64.py); agreement with any outside toolkit is unpinned.
+ *
+ * snf_dtw_detect: the arguments, the lattice, score[j] and the curves of snf_dtw_search.  Of pair p every end j is
+ * alive at first, and up to K = `max_detections` rounds follow:
+ *   e = the smallest alive j of minimal score (a strict < over ascending j); stop if not score[e] <= max_score
+ *   (a float32 comparison; +inf: no threshold); detection r = d_count[p] so far is d_end[p K + r] = e,
+ *   d_start[p K + r] = B[N-1][e], d_cost[p K + r] = C[N-1][e], d_len[p K + r] = L[N-1][e];
+ *   every end j' whose path interval [B[N-1][j'], j'] shares a frame with [B[N-1][e], e] dies (e among them).
+ * It stops after K detections or when no end is alive.  d_count[p] detections come in ascending score, their
+ * intervals are pairwise disjoint, and rank 0 is what snf_dtw_search returns.  Every element of d_count [P] and of
+ * the four arrays [P K] is written: a slot at or beyond d_count[p] holds cost = +inf, len = 0, start = end = -1.
+ * Results are in the caller's pair order and a pair's result does not depend on the other pairs of the call.
+ * Non-finite features give undefined values, nothing worse.
+ * SNF_E_INVALID, before any device work: what snf_dtw_search refuses, max_detections outside
+ * [1, SNF_DTW_MAX_DETECTIONS], a NaN max_score.  n_pairs = 0 does nothing.  Streams and slots: as snf_dtw_pairs. */
+#define SNF_DTW_MAX_DETECTIONS 64
+int snf_dtw_detect(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                   const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs /* (query, target) */,
+                   int64_t n_pairs, int32_t metric, int32_t normalized, int32_t max_detections, float max_score,
+                   int32_t* d_count, float* d_cost, int32_t* d_len, int32_t* d_start, int32_t* d_end,
+                   const int64_t* h_curve_first, float* d_curve_cost, int32_t* d_curve_len, int32_t* d_curve_start,
+                   void* stream);
+/* snf_dtw_topk: per query the T = `top_k` best detections of what snf_dtw_detect left on the device (d_count [P],
+ * d_cost, d_len, d_start, d_end [P K], K = `max_detections` of that call; they are read where they lie).  The HOST
+ * tables say which pairs belong to which query: query q owns h_group_pairs[h_group_first[q] ..
+ * h_group_first[q + 1]), pair indices in [0, n_pairs) (a stable grouping of the caller's pair order;
+ * h_group_first [Q + 1] starts at 0 and does not descend).  The candidates of a query are the first d_count[p]
+ * slots of its pairs, never a sentinel slot.  They are ordered by the key (score, pair index, rank), the score being
+ * d_cost / (float)d_len (the correctly rounded float32 division) if `normalized`, else d_cost; place i < d_top_count[q]
+ * of query q is at q T + i of d_top_pair, d_top_rank, d_top_cost, d_top_len, d_top_start, d_top_end.  Every element
+ * of d_top_count [Q] and of the six arrays [Q T] is written: a place at or beyond the count holds pair = rank = -1,
+ * cost = +inf, len = 0, start = end = -1.  A pair listed twice is a candidate once (keys are compared, not slots).
+ * SNF_E_INVALID, before any device work: max_detections outside [1, SNF_DTW_MAX_DETECTIONS], top_k outside
+ * [1, SNF_DTW_MAX_TOPK], `normalized` not 0 or 1, negative sizes, group boundaries that do not start at 0 or descend,
+ * a grouped pair outside [0, n_pairs), a null or misaligned pointer.  n_queries = 0 does nothing.  One wavefront
+ * works per query, T passes over its candidates: meant for T up to the limit and pairs per query in the tens of
+ * thousands.  Streams and slots: as snf_dtw_pairs. */
+#define SNF_DTW_MAX_TOPK 1024
+int snf_dtw_topk(int device_id, const int32_t* d_count, const float* d_cost, const int32_t* d_len,
+                 const int32_t* d_start, const int32_t* d_end, int64_t n_pairs, int32_t max_detections,
+                 int32_t normalized, const int32_t* h_group_pairs, const int64_t* h_group_first, int64_t n_queries,
+                 int32_t top_k, int32_t* d_top_count, int32_t* d_top_pair, int32_t* d_top_rank, float* d_top_cost,
+                 int32_t* d_top_len, int32_t* d_top_start, int32_t* d_top_end, void* stream);
+
 /* ---- ABX triplet counts over a table of distances (the two steps after the distances in the reference's examples) --
  * An extension with no reference call behind it: the reference's examples run `abx-score` and `abx-analyze` of an
  * external toolkit on the CPU (reference examples/features_abx/scripts/abx_score.sh:22-23), one triplet at a time,

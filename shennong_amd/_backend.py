@@ -49,7 +49,8 @@ EXPORTS = [
     'snf_pack_weights_bf16', 'snf_dense_layer_bf16', 'snf_bottleneck_forward_bf16', 'snf_crepe_conv_bf16',
     'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
     'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs',
-    'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs', 'snf_dtw_search', 'snf_abx_cells']
+    'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs', 'snf_dtw_search', 'snf_dtw_detect', 'snf_dtw_topk',
+    'snf_abx_cells']
 
 
 _OOM_HOOK_TYPE = C.CFUNCTYPE(None)
@@ -208,6 +209,10 @@ def lib():
         L.snf_dtw_pairs.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, vp, vp, vp]
         L.snf_dtw_search.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, i32, vp, vp, vp, vp, pi64, vp, vp,
                                      vp, vp]
+        L.snf_dtw_detect.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, i32, i32, f32, vp, vp, vp, vp, vp,
+                                     pi64, vp, vp, vp, vp]
+        L.snf_dtw_topk.argtypes = [i32, vp, vp, vp, vp, vp, i64, i32, i32, pi32, pi64, i64, i32, vp, vp, vp, vp, vp,
+                                   vp, vp, vp]
         L.snf_abx_cells.argtypes = [i32, vp, vp, i64, pi64, i64, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
@@ -1085,6 +1090,62 @@ def dtw_search(d_rows, dim, item_first, item_count, pairs, metric, normalized, d
         C.c_void_p(d_cost), C.c_void_p(d_len), C.c_void_p(d_start), C.c_void_p(d_end),
         curves.ctypes.data_as(C.POINTER(C.c_int64)) if curves is not None else None,
         pointer(d_curve_cost), pointer(d_curve_len), pointer(d_curve_start), C.c_void_p(stream) if stream else None))
+
+
+DTW_MAX_DETECTIONS = 64                          # SNF_DTW_MAX_DETECTIONS
+DTW_MAX_TOPK = 1024                              # SNF_DTW_MAX_TOPK
+
+
+def dtw_detect(d_rows, dim, item_first, item_count, pairs, metric, normalized, max_detections, max_score, d_count,
+               d_cost, d_len, d_start, d_end, curve_first=None, d_curve_cost=None, d_curve_len=None,
+               d_curve_start=None, device=None, stream=None):
+    """Up to `max_detections` non-overlapping detections of every (query, target) pair of `pairs` [P, 2] over the
+    items of ``dtw_pairs``: their number (int32 [P] at `d_count`) and cost (float32), path length, start and end
+    frame (int32) at the four device pointers [P * max_detections]; `max_score` None: no threshold; the curves of
+    ``dtw_search``.  See snf_dtw_detect in include/shennong_amd.h"""
+    first = np.ascontiguousarray(item_first, dtype=np.int64)
+    count = np.ascontiguousarray(item_count, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if metric not in DTW_METRICS:
+        raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(DTW_METRICS)))
+    curves = None
+    if curve_first is not None:
+        curves = np.ascontiguousarray(curve_first, dtype=np.int64).reshape(-1)
+        if curves.shape[0] != pairs.shape[0]:
+            raise ValueError('curve_first has {} entries for {} pairs'.format(curves.shape[0], pairs.shape[0]))
+        if curves.shape[0] == 0:   # (ctypes gives no address of an empty array: any non-null one says "curves")
+            curves = np.zeros(1, dtype=np.int64)
+    pointer = lambda d: C.c_void_p(d) if d else None   # noqa: E731
+    check(lib().snf_dtw_detect(
+        _DEVICE if device is None else int(device), C.c_void_p(d_rows), int(dim),
+        first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int32)), first.shape[0],
+        pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], DTW_METRICS[metric], int(bool(normalized)),
+        int(max_detections), float('inf') if max_score is None else float(max_score),
+        C.c_void_p(d_count), C.c_void_p(d_cost), C.c_void_p(d_len), C.c_void_p(d_start), C.c_void_p(d_end),
+        curves.ctypes.data_as(C.POINTER(C.c_int64)) if curves is not None else None,
+        pointer(d_curve_cost), pointer(d_curve_len), pointer(d_curve_start), C.c_void_p(stream) if stream else None))
+
+
+def dtw_topk(d_count, d_cost, d_len, d_start, d_end, n_pairs, max_detections, normalized, group_pairs, group_first,
+             top_k, d_top_count, d_top_pair, d_top_rank, d_top_cost, d_top_len, d_top_start, d_top_end, device=None,
+             stream=None):
+    """The `top_k` best detections per query of what ``dtw_detect`` left at its five device pointers: query q owns
+    the pairs ``group_pairs[group_first[q]:group_first[q + 1]]`` (host arrays); the count (int32 [Q]) and pair, rank,
+    cost, length, start and end ([Q * top_k]) go to the seven device pointers.  See snf_dtw_topk in
+    include/shennong_amd.h"""
+    group_pairs = np.ascontiguousarray(group_pairs, dtype=np.int32).reshape(-1)
+    group_first = np.ascontiguousarray(group_first, dtype=np.int64).reshape(-1)
+    if group_first.shape[0] < 1:
+        raise ValueError('group_first must hold the boundaries of the groups, [Q + 1]')
+    if group_pairs.shape[0] == 0:   # (ctypes gives no address of an empty array)
+        group_pairs = np.zeros(1, dtype=np.int32)
+    check(lib().snf_dtw_topk(
+        _DEVICE if device is None else int(device), C.c_void_p(d_count), C.c_void_p(d_cost), C.c_void_p(d_len),
+        C.c_void_p(d_start), C.c_void_p(d_end), int(n_pairs), int(max_detections), int(bool(normalized)),
+        group_pairs.ctypes.data_as(C.POINTER(C.c_int32)), group_first.ctypes.data_as(C.POINTER(C.c_int64)),
+        group_first.shape[0] - 1, int(top_k), C.c_void_p(d_top_count), C.c_void_p(d_top_pair),
+        C.c_void_p(d_top_rank), C.c_void_p(d_top_cost), C.c_void_p(d_top_len), C.c_void_p(d_top_start),
+        C.c_void_p(d_top_end), C.c_void_p(stream) if stream else None))
 
 
 def abx_cells(d_cost, d_len, n_dist, cells, d_counts, device=None, stream=None):

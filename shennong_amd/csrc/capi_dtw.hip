@@ -1,10 +1,13 @@
 // C ABI of libshennong_hip.so (include/shennong_amd.h): DTW cost and path length of pairs of feature items
-// (snf_dtw_pairs) and subsequence DTW search of queries in targets (snf_dtw_search).  Every argument is checked on
+// (snf_dtw_pairs), subsequence DTW search of queries in targets (snf_dtw_search), several detections per such pair
+// (snf_dtw_detect) and the best few detections per query (snf_dtw_topk).  Every argument is checked on
 // the host before any device is asked for.  The host sorts the pairs by kernel class and, within a class, by the
 // cells of their lattice descending (kernels_dtw.hip).  The item and pair tables go up on the calling thread's own
 // stream (waited for) into a slot that stays reserved, with the row norms of the call, until the kernels, enqueued
-// on the caller's stream, have run - so the call does not wait for the caller's stream.  Both calls share the
-// checks of the tables (check_tables), the sort (sort_pairs) and the slot protocol (enqueue).
+// on the caller's stream, have run - so the call does not wait for the caller's stream.  The pair calls share the
+// checks of the tables (check_tables), the sort (sort_pairs) and the slot protocol (enqueue); search and detection
+// also the checks of the curves (check_curves).  snf_dtw_topk has group tables in the place of the item and pair
+// tables and keeps them in a slot in the same way.
 #include <algorithm>
 #include <memory>
 
@@ -174,6 +177,33 @@ int enqueue(const std::string& who, int device_id, void* stream, const DtwTables
 
 bool bad_word_pointer(const void* p) { return !p || (reinterpret_cast<uintptr_t>(p) & 3); }
 
+// The curves of a search or a detection: pair p owns the elements [first, first + M) of the three curve arrays,
+// inside [0, 2^31), and no two overlap
+int check_curves(const std::string& who, const DtwTables& t, const int32_t* h_pairs, int64_t n_pairs,
+                 const int64_t* h_curve_first, const float* d_curve_cost, const int32_t* d_curve_len,
+                 const int32_t* d_curve_start, std::vector<int64_t>& curve_first) {
+  if (bad_word_pointer(d_curve_cost) || bad_word_pointer(d_curve_len) || bad_word_pointer(d_curve_start))
+    return set_error(SNF_E_INVALID, who + ": a curve array is not 4-byte aligned");
+  curve_first.assign(h_curve_first, h_curve_first + n_pairs);
+  std::vector<std::pair<int64_t, int32_t>> stretch(static_cast<size_t>(n_pairs));   // (first, pair)
+  for (int64_t p = 0; p < n_pairs; ++p) {
+    const int64_t first = curve_first[p], columns = t.items[h_pairs[2 * p + 1]].frames;
+    if (first < 0 || first + columns > (int64_t(1) << 31))
+      return set_error(SNF_E_INVALID, who + ": the curve of pair " + std::to_string(p) + " (" +
+                                          std::to_string(columns) + " elements at " + std::to_string(first) +
+                                          ") lies outside [0, 2^31)");
+    stretch[p] = {first, static_cast<int32_t>(p)};
+  }
+  std::sort(stretch.begin(), stretch.end());
+  for (int64_t k = 0; k + 1 < n_pairs; ++k) {
+    const int32_t a = stretch[k].second, b = stretch[k + 1].second;
+    if (stretch[k].first + t.items[h_pairs[2 * a + 1]].frames > stretch[k + 1].first)
+      return set_error(SNF_E_INVALID, who + ": the curves of the pairs " + std::to_string(std::min(a, b)) +
+                                          " and " + std::to_string(std::max(a, b)) + " overlap");
+  }
+  return SNF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -216,28 +246,10 @@ int snf_dtw_search(int device_id, const float* d_rows, int32_t dim, const int64_
   if (bad_word_pointer(d_cost) || bad_word_pointer(d_len) || bad_word_pointer(d_start) || bad_word_pointer(d_end))
     return set_error(SNF_E_INVALID, who + ": d_cost, d_len, d_start or d_end is null or not 4-byte aligned");
   std::vector<int64_t> curve_first;
-  if (curve_pointers) {
-    if (bad_word_pointer(d_curve_cost) || bad_word_pointer(d_curve_len) || bad_word_pointer(d_curve_start))
-      return set_error(SNF_E_INVALID, who + ": a curve array is not 4-byte aligned");
-    // pair p owns the elements [first, first + M) of the three curve arrays: inside [0, 2^31), and no two overlap
-    curve_first.assign(h_curve_first, h_curve_first + n_pairs);
-    std::vector<std::pair<int64_t, int32_t>> stretch(static_cast<size_t>(n_pairs));   // (first, pair)
-    for (int64_t p = 0; p < n_pairs; ++p) {
-      const int64_t first = curve_first[p], columns = t.items[h_pairs[2 * p + 1]].frames;
-      if (first < 0 || first + columns > (int64_t(1) << 31))
-        return set_error(SNF_E_INVALID, who + ": the curve of pair " + std::to_string(p) + " (" +
-                                            std::to_string(columns) + " elements at " + std::to_string(first) +
-                                            ") lies outside [0, 2^31)");
-      stretch[p] = {first, static_cast<int32_t>(p)};
-    }
-    std::sort(stretch.begin(), stretch.end());
-    for (int64_t k = 0; k + 1 < n_pairs; ++k) {
-      const int32_t a = stretch[k].second, b = stretch[k + 1].second;
-      if (stretch[k].first + t.items[h_pairs[2 * a + 1]].frames > stretch[k + 1].first)
-        return set_error(SNF_E_INVALID, who + ": the curves of the pairs " + std::to_string(std::min(a, b)) +
-                                            " and " + std::to_string(std::max(a, b)) + " overlap");
-    }
-  }
+  if (curve_pointers)
+    if (const int rc = check_curves(who, t, h_pairs, n_pairs, h_curve_first, d_curve_cost, d_curve_len, d_curve_start,
+                                    curve_first))
+      return rc;
   if (const int rc = sort_pairs(who, t)) return rc;
   return enqueue(who, device_id, stream, t, dim, metric, curve_pointers ? &curve_first : nullptr,
                  [&](DtwSlot& slot, int compute_units, hipStream_t s) {
@@ -248,6 +260,119 @@ int snf_dtw_search(int device_id, const float* d_rows, int32_t dim, const int64_
                                             t.class_count, t.row_lo, t.row_hi, slot.aux.as<float>(), metric,
                                             normalized, compute_units, out, s);
                  });
+}
+
+int snf_dtw_detect(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                   const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
+                   int32_t metric, int32_t normalized, int32_t max_detections, float max_score, int32_t* d_count,
+                   float* d_cost, int32_t* d_len, int32_t* d_start, int32_t* d_end, const int64_t* h_curve_first,
+                   float* d_curve_cost, int32_t* d_curve_len, int32_t* d_curve_start, void* stream) {
+  const std::string who = "dtw_detect";
+  DtwTables t;
+  if (const int rc = check_tables(who, dim, metric, h_item_first, h_item_count, n_items, h_pairs, n_pairs, t))
+    return rc;
+  if (normalized != 0 && normalized != 1) return set_error(SNF_E_INVALID, who + ": normalized must be 0 or 1");
+  if (max_detections < 1 || max_detections > kDtwMaxDetections)
+    return set_error(SNF_E_INVALID, who + ": max_detections must be in [1, " + std::to_string(kDtwMaxDetections) +
+                                        "], not " + std::to_string(max_detections));
+  if (max_score != max_score) return set_error(SNF_E_INVALID, who + ": max_score is not a number");
+  const int curve_pointers = (h_curve_first != nullptr) + (d_curve_cost != nullptr) + (d_curve_len != nullptr) +
+                             (d_curve_start != nullptr);
+  if (curve_pointers != 0 && curve_pointers != 4)
+    return set_error(SNF_E_INVALID, who + ": the curve pointers must be all set or all null");
+  if (n_pairs == 0) return SNF_OK;
+  if (bad_word_pointer(d_rows))
+    return set_error(SNF_E_INVALID, who + ": d_rows is null or not aligned to float32");
+  if (bad_word_pointer(d_count) || bad_word_pointer(d_cost) || bad_word_pointer(d_len) || bad_word_pointer(d_start) ||
+      bad_word_pointer(d_end))
+    return set_error(SNF_E_INVALID,
+                     who + ": d_count, d_cost, d_len, d_start or d_end is null or not 4-byte aligned");
+  std::vector<int64_t> curve_first;
+  if (curve_pointers)
+    if (const int rc = check_curves(who, t, h_pairs, n_pairs, h_curve_first, d_curve_cost, d_curve_len, d_curve_start,
+                                    curve_first))
+      return rc;
+  if (const int rc = sort_pairs(who, t)) return rc;
+  return enqueue(who, device_id, stream, t, dim, metric, curve_pointers ? &curve_first : nullptr,
+                 [&](DtwSlot& slot, int compute_units, hipStream_t s) {
+                   const DtwDetectOut out = {d_count, d_cost, d_len, d_start, d_end, max_detections, max_score,
+                                             curve_pointers ? slot.curves.as<int64_t>() : nullptr,
+                                             d_curve_cost, d_curve_len, d_curve_start};
+                   return launch_dtw_detect(d_rows, dim, slot.items.as<DtwItem>(), slot.pairs.as<DtwPair>(),
+                                            t.class_count, t.row_lo, t.row_hi, slot.aux.as<float>(), metric,
+                                            normalized, compute_units, out, s);
+                 });
+}
+
+int snf_dtw_topk(int device_id, const int32_t* d_count, const float* d_cost, const int32_t* d_len,
+                 const int32_t* d_start, const int32_t* d_end, int64_t n_pairs, int32_t max_detections,
+                 int32_t normalized, const int32_t* h_group_pairs, const int64_t* h_group_first, int64_t n_queries,
+                 int32_t top_k, int32_t* d_top_count, int32_t* d_top_pair, int32_t* d_top_rank, float* d_top_cost,
+                 int32_t* d_top_len, int32_t* d_top_start, int32_t* d_top_end, void* stream) {
+  const std::string who = "dtw_topk";
+  if (n_pairs < 0 || n_pairs > 0x7fffffff) return set_error(SNF_E_INVALID, who + ": number of pairs out of range");
+  if (n_queries < 0 || n_queries > 0x7fffffff)
+    return set_error(SNF_E_INVALID, who + ": number of queries out of range");
+  if (max_detections < 1 || max_detections > kDtwMaxDetections)
+    return set_error(SNF_E_INVALID, who + ": max_detections must be in [1, " + std::to_string(kDtwMaxDetections) +
+                                        "], not " + std::to_string(max_detections));
+  if (normalized != 0 && normalized != 1) return set_error(SNF_E_INVALID, who + ": normalized must be 0 or 1");
+  if (top_k < 1 || top_k > kDtwMaxTopk)
+    return set_error(SNF_E_INVALID, who + ": top_k must be in [1, " + std::to_string(kDtwMaxTopk) + "], not " +
+                                        std::to_string(top_k));
+  if (n_queries == 0) return SNF_OK;
+  if (!h_group_first) return set_error(SNF_E_INVALID, who + ": null group table");
+  if (h_group_first[0] != 0) return set_error(SNF_E_INVALID, who + ": the first group must start at 0");
+  for (int64_t q = 0; q < n_queries; ++q)
+    if (h_group_first[q + 1] < h_group_first[q] || h_group_first[q + 1] > 0x7fffffff)
+      return set_error(SNF_E_INVALID, who + ": the group of query " + std::to_string(q) + " ends before it starts" +
+                                          " or beyond 2^31 - 1");
+  const int64_t grouped = h_group_first[n_queries];
+  if (grouped > 0 && !h_group_pairs) return set_error(SNF_E_INVALID, who + ": null group table");
+  for (int64_t g = 0; g < grouped; ++g)
+    if (h_group_pairs[g] < 0 || h_group_pairs[g] >= n_pairs)
+      return set_error(SNF_E_INVALID, who + ": grouped pair " + std::to_string(g) + " (" +
+                                          std::to_string(h_group_pairs[g]) + ") is out of range for " +
+                                          std::to_string(n_pairs) + " pairs");
+  if (grouped > 0 && (bad_word_pointer(d_count) || bad_word_pointer(d_cost) || bad_word_pointer(d_len) ||
+                      bad_word_pointer(d_start) || bad_word_pointer(d_end)))
+    return set_error(SNF_E_INVALID,
+                     who + ": d_count, d_cost, d_len, d_start or d_end is null or not 4-byte aligned");
+  if (bad_word_pointer(d_top_count) || bad_word_pointer(d_top_pair) || bad_word_pointer(d_top_rank) ||
+      bad_word_pointer(d_top_cost) || bad_word_pointer(d_top_len) || bad_word_pointer(d_top_start) ||
+      bad_word_pointer(d_top_end))
+    return set_error(SNF_E_INVALID, who + ": an output array is null or not 4-byte aligned");
+
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return set_error(SNF_E_NODEVICE, "no HIP device visible: libshennong_hip needs an MI355X (gfx950)");
+  if (device_id < 0 || device_id >= ndev) return set_error(SNF_E_INVALID, "bad device id");
+  SNF_HIP_CHECK(hipSetDevice(device_id));
+  ThreadScratch* mine = thread_scratch(device_id);
+  if (!mine) return SNF_E_HIP;
+  DtwSlot* slot = take_slot(device_id);
+  if (!slot) return SNF_E_HIP;
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : mine->stream;
+  // (the group tables take the place of the item and pair tables in the slot)
+  const std::vector<int32_t> group_pairs(h_group_pairs, h_group_pairs + grouped);
+  const std::vector<int64_t> group_first(h_group_first, h_group_first + n_queries + 1);
+  int rc = slot->items.upload(group_pairs, mine->stream);
+  if (!rc) rc = slot->pairs.upload(group_first, mine->stream);
+  if (!rc) {
+    const DtwTopkIn in = {d_count, d_cost, d_len, d_start, d_end, max_detections, slot->items.as<int32_t>(),
+                          slot->pairs.as<int64_t>()};
+    const DtwTopkOut out = {d_top_count, d_top_pair, d_top_rank, d_top_cost, d_top_len, d_top_start, d_top_end};
+    rc = launch_dtw_topk(in, n_queries, top_k, normalized, out, s);
+  }
+  if (!rc && hipEventRecord(slot->done, s) != hipSuccess) rc = set_error(SNF_E_HIP, who + ": hipEventRecord failed");
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    give_slot(slot);
+    return rc;
+  }
+  give_slot(slot);
+  if (!stream && hipStreamSynchronize(s) != hipSuccess) return set_error(SNF_E_HIP, who + " kernel failed");
+  return SNF_OK;
 }
 
 }  // extern "C"

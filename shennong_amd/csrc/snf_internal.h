@@ -454,6 +454,40 @@ struct DtwSearchOut {
 int launch_dtw_search(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
                       const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
                       int normalized, int compute_units, const DtwSearchOut& out, hipStream_t stream);
+// kernels_dtw_detect.hip: up to `k` detections per pair, a greedy non-maximum suppression over the ends of the same
+// lattice, behind it in the same wave (snf_dtw_detect); and the best `t` detections per query of what it left in
+// HBM (snf_dtw_topk)
+constexpr int kDtwMaxDetections = 64;   // SNF_DTW_MAX_DETECTIONS
+constexpr int kDtwMaxTopk = 1024;       // SNF_DTW_MAX_TOPK
+struct DtwDetectOut {
+  int32_t* count;                // [P] in the caller's pair order
+  float* cost;                   // [P * k]: pair p, rank r at p * k + r, as len, start, end
+  int32_t *len, *start, *end;
+  int32_t k;                     // 1 <= k <= kDtwMaxDetections
+  float max_score;               // a detection needs score <= max_score (+inf: every one does)
+  const int64_t* curve_first;    // the curves of DtwSearchOut
+  float* curve_cost;
+  int32_t *curve_len, *curve_start;
+};
+int launch_dtw_detect(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
+                      const int64_t* class_count, int64_t row_lo, int64_t row_hi, float* d_aux, int metric,
+                      int normalized, int compute_units, const DtwDetectOut& out, hipStream_t stream);
+struct DtwTopkIn {
+  const int32_t* count;          // the arrays that snf_dtw_detect wrote, k slots per pair
+  const float* cost;
+  const int32_t *len, *start, *end;
+  int32_t k;
+  const int32_t* group_pair;     // device: the pair indices grouped by query
+  const int64_t* group_first;    // device [Q + 1]: query q owns group_pair[group_first[q] .. group_first[q + 1])
+};
+struct DtwTopkOut {
+  int32_t* count;                // [Q]
+  int32_t *pair, *rank;          // [Q * t]: query q, place i at q * t + i, as cost, len, start, end
+  float* cost;
+  int32_t *len, *start, *end;
+};
+int launch_dtw_topk(const DtwTopkIn& in, int64_t n_queries, int top_k, int normalized, const DtwTopkOut& out,
+                    hipStream_t stream);
 
 // kernels_abx.hip: ABX triplet counts per cell over a table of distances (snf_abx_cells)
 constexpr int kAbxTile = 1024;        // floats of a B-row staged in LDS at a time (4 KB per wave)

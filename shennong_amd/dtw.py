@@ -32,6 +32,13 @@ snf_dtw_search; its docstring has the definition, DESIGN section 4.17 the rest):
     found = dtw_search(feats, queries=[('utt1', 0.31, 0.52)], targets=['utt2', 'utt3'])    # a DtwMatches
     best = found.ranked(0)[0]                         # the pair of query 0 with the smallest score
     found.target[best], found.onset[best], found.offset[best]
+
+:func:`dtw_detect` finds every place a query occurs in a target, not only the best one, and the best few hits of a
+query over a whole corpus, all picked on the device (snf_dtw_detect, snf_dtw_topk):
+
+    hits = dtw_detect(feats, queries, targets, max_detections=4, top_k=10)                  # a DtwDetections
+    rows = hits.ranked(0)                             # the rows of query 0, the best first
+    hits.target[rows], hits.onset[rows], hits.offset[rows]
 """
 
 import numpy as np
@@ -39,7 +46,7 @@ import numpy as np
 from shennong_amd import _backend
 from shennong_amd.device import DeviceFeaturesCollection
 
-__all__ = ['dtw_distances', 'dtw_search', 'DtwMatches', 'MAX_FRAMES']
+__all__ = ['dtw_distances', 'dtw_search', 'dtw_detect', 'DtwMatches', 'DtwDetections', 'MAX_FRAMES']
 
 MAX_FRAMES = _backend.DTW_MAX_FRAMES
 
@@ -278,6 +285,26 @@ def _select_search(features, queries, targets, pairs):
     return (np.array(first, dtype=np.int64), count.astype(np.int32), pairs, n_queries, where[n_queries:], dim, block)
 
 
+def _times(features, where, target, start, end):
+    """(onset, offset) in seconds of the paths from frame `start` to frame `end` of the targets `target` (indices
+    into `where`, which ``_select_search`` returns): the start time of the start row and the stop time of the end
+    row of the target's utterance ([n, 2] times), or their single time ([n] times)"""
+    # the start and stop times of the targets' utterances laid end to end, and per target the place of its first
+    # row in them
+    placed, begins, ends, rows = {}, [np.zeros(0)], [np.zeros(0)], 0
+    base = np.zeros(len(where), dtype=np.int64)
+    for t, (name, row) in enumerate(where):
+        if name not in placed:
+            stamps = np.asarray(features[name].times, dtype=np.float64)
+            begins.append(stamps[:, 0] if stamps.ndim == 2 else stamps)
+            ends.append(stamps[:, 1] if stamps.ndim == 2 else stamps)
+            placed[name] = rows
+            rows += stamps.shape[0]
+        base[t] = placed[name] + row
+    at = base[target] if len(target) else np.zeros(0, dtype=np.int64)
+    return np.concatenate(begins)[at + start], np.concatenate(ends)[at + end]
+
+
 def dtw_search(features, queries, targets, pairs=None, metric='cosine', normalized=True, return_curves=False):
     """Query-by-example search: where does every query occur in every target?  Subsequence DTW on the GPU
     (snf_dtw_search), a :class:`DtwMatches` with the best match of every (query, target) pair
@@ -352,18 +379,189 @@ def dtw_search(features, queries, targets, pairs=None, metric='cosine', normaliz
             if owned is not None:
                 owned.release()
     score = cost / length.astype(np.float32) if normalized and n_pairs else cost.copy()
-    # the times of the matches: the start and stop times of the targets' utterances laid end to end, and per target
-    # the place of its first row in them
-    placed, begins, ends, rows = {}, [np.zeros(0)], [np.zeros(0)], 0
-    base = np.zeros(len(where), dtype=np.int64)
-    for t, (name, row) in enumerate(where):
-        if name not in placed:
-            stamps = np.asarray(features[name].times, dtype=np.float64)
-            begins.append(stamps[:, 0] if stamps.ndim == 2 else stamps)
-            ends.append(stamps[:, 1] if stamps.ndim == 2 else stamps)
-            placed[name] = rows
-            rows += stamps.shape[0]
-        base[t] = placed[name] + row
-    at = base[pairs[:, 1]] if n_pairs else np.zeros(0, dtype=np.int64)
-    onset, offset = np.concatenate(begins)[at + start], np.concatenate(ends)[at + end]
+    onset, offset = _times(features, where, pairs[:, 1], start, end)
     return DtwMatches(pairs[:, 0], pairs[:, 1], score, cost, length, start, end, onset, offset, curves)
+
+
+class DtwDetections:
+    """The detections of a :func:`dtw_detect`: numpy columns, one row per detection
+
+    `pair` (int32): the index of the (query, target) pair in the pairs of the call; `query`, `target` (int32): the
+    indices of its query and its target; `rank` (int32): 0 for the best detection of the pair, 1 for the next ...
+    `score`, `cost` (float32), `length`, `start_frame`, `end_frame` (int32), `onset`, `offset` (float64 seconds): as
+    the columns of :class:`DtwMatches`.
+
+    Without `top_k` the rows are in the order of the pairs, then by rank, and `counts` [P] holds the detections of
+    every pair.  With `top_k` the rows are in the order of the queries, then by (score, pair, rank), and `counts`
+    [Q] holds the rows of every query."""
+
+    columns = ('pair', 'query', 'target', 'rank', 'score', 'cost', 'length', 'start_frame', 'end_frame', 'onset',
+               'offset')
+    _types = (np.int32, np.int32, np.int32, np.int32, np.float32, np.float32, np.int32, np.int32, np.int32,
+              np.float64, np.float64)
+
+    def __init__(self, pair, query, target, rank, score, cost, length, start_frame, end_frame, onset, offset,
+                 counts, curves=None, top_k=None):
+        given = (pair, query, target, rank, score, cost, length, start_frame, end_frame, onset, offset)
+        for name, column, dtype in zip(self.columns, given, self._types):
+            setattr(self, name, np.asarray(column, dtype=dtype))
+        sizes = {getattr(self, name).shape for name in self.columns}
+        if len(sizes) != 1 or len(next(iter(sizes))) != 1:
+            raise ValueError('the columns must be one-dimensional and of one length: {}'.format(sorted(sizes)))
+        self.counts = np.asarray(counts, dtype=np.int32)
+        if self.counts.ndim != 1 or int(self.counts.sum()) != len(self):
+            raise ValueError('counts must be one-dimensional and sum to the {} rows'.format(len(self)))
+        self.top_k = top_k
+        # (first [P + 1], cost, length, start): pair p owns the elements first[p] .. first[p + 1] of the three
+        self._curves = curves
+
+    def __len__(self):
+        return self.pair.shape[0]
+
+    def of_pair(self, p):
+        """The rows of pair `p`, by ascending rank"""
+        return np.flatnonzero(self.pair == p)
+
+    def ranked(self, query):
+        """The rows of query `query` by ascending (score, pair, rank)"""
+        mine = np.flatnonzero(self.query == query)
+        mine = mine[np.lexsort((self.rank[mine], self.pair[mine]))]
+        return mine[np.argsort(self.score[mine], kind='stable')]
+
+    def curve(self, p):
+        """``(cost [M], length [M], start [M])`` of pair `p`, as ``DtwMatches.curve``: what the detections of the
+        pair were picked from.  ValueError when the call did not ask for curves"""
+        if self._curves is None:
+            raise ValueError('no curves: call dtw_detect with return_curves=True')
+        first, cost, length, start = self._curves
+        n_pairs = first.shape[0] - 1
+        if not -n_pairs <= p < n_pairs:
+            raise IndexError('pair {} is out of range for {} pairs'.format(p, n_pairs))
+        p = p % n_pairs
+        lo, hi = int(first[p]), int(first[p + 1])
+        return cost[lo:hi], length[lo:hi], start[lo:hi]
+
+    def save_csv(self, path):
+        """Writes the rows to `path`: a header line with the names of the columns, then one line per detection
+        (floats with the digits that give the same value back)"""
+        with open(path, 'w') as out:
+            out.write(','.join(self.columns) + '\n')
+            values = [getattr(self, name).tolist() for name in self.columns]
+            for row in zip(*values):
+                out.write(','.join(repr(v) for v in row) + '\n')
+
+
+def _int_in(value, lo, hi):
+    return isinstance(value, (int, np.integer)) and not isinstance(value, (bool, np.bool_)) and lo <= value <= hi
+
+
+def dtw_detect(features, queries, targets, pairs=None, metric='cosine', normalized=True, max_detections=4,
+               max_score=None, top_k=None, return_curves=False):
+    """Query-by-example detection: every place a query occurs in a target, not only the best one (snf_dtw_detect), and
+    per query the best few over all its targets (snf_dtw_topk); a :class:`DtwDetections`
+
+    The lattice, the score of an end and the arguments `features`, `queries`, `targets`, `pairs`, `metric`,
+    `normalized` and `return_curves` are those of :func:`dtw_search`.  The detections of a pair are a greedy
+    non-maximum suppression over its ends; every end is alive at first, and then, at most `max_detections` times:
+
+        e = the smallest alive end of minimal score; stop if `max_score` is given and not score[e] <= max_score
+        (a float32 comparison); (score, cost, length, start, end) of e is the detection of the next rank; every end
+        whose path interval [start, end] shares a frame with that of e is no longer alive
+
+    So the detections of a pair come in ascending score, their intervals in the target are pairwise disjoint, and
+    rank 0 is the match of ``dtw_search``.  The definition is this project's own (tests/dtw_detect_f64.py states
+    it); agreement with any outside toolkit is not pinned.
+
+    `top_k` T: per query only its T best detections, by (score ascending, pair index, rank), are selected on the
+    device and downloaded - Q T records instead of P max_detections.
+
+    ValueError, before any device work: what ``dtw_search`` raises, `max_detections` not an int in [1, 64], `top_k`
+    not an int in [1, 1024], a NaN `max_score`, `top_k` together with `return_curves`."""
+    if metric not in _backend.DTW_METRICS:
+        raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(_backend.DTW_METRICS)))
+    if not _int_in(max_detections, 1, _backend.DTW_MAX_DETECTIONS):
+        raise ValueError('max_detections must be an int in [1, {}], not {!r}'.format(
+            _backend.DTW_MAX_DETECTIONS, max_detections))
+    if top_k is not None and not _int_in(top_k, 1, _backend.DTW_MAX_TOPK):
+        raise ValueError('top_k must be None or an int in [1, {}], not {!r}'.format(_backend.DTW_MAX_TOPK, top_k))
+    if max_score is not None:
+        max_score = float(max_score)
+        if max_score != max_score:
+            raise ValueError('max_score must be None or a number, not {!r}'.format(max_score))
+    if top_k is not None and return_curves:
+        raise ValueError('top_k={} with return_curves=True: the curves are per pair, ask for them without top_k'
+                         .format(top_k))
+    first, count, pairs, n_queries, where, dim, block = _select_search(features, queries, targets, pairs)
+    n_pairs, k = pairs.shape[0], int(max_detections)
+    columns = count[n_queries + pairs[:, 1]].astype(np.int64)   # M of every pair
+    curve_first = np.concatenate([[0], np.cumsum(columns)]).astype(np.int64)
+    total = int(curve_first[-1])
+    if return_curves and total >= 2 ** 31:
+        raise ValueError('the curves of the {} pairs hold {} elements, the limit is 2^31 - 1: search in parts'.format(
+            n_pairs, total))
+    # what comes down: per pair k slots, or per query top_k places
+    groups, slots = (n_pairs, k) if top_k is None else (n_queries, int(top_k))
+    counts = np.zeros(groups, dtype=np.int32)
+    cost = np.zeros(groups * slots, dtype=np.float32)
+    length, start, end = (np.zeros(groups * slots, dtype=np.int32) for _ in range(3))
+    top_pair, top_rank = (np.zeros(groups * slots, dtype=np.int32) for _ in range(2))
+    curves = None
+    if return_curves:
+        curves = (curve_first, np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.int32),
+                  np.zeros(total, dtype=np.int32))
+    if n_pairs:
+        owned = None
+        if block is None:
+            owned = DeviceFeaturesCollection.from_host(features)
+            block = owned._blocks[0]
+        buffers = []
+        try:
+            buffer = block.alive()
+            buffers.append(_backend.DeviceBuffer(4 * n_pairs, buffer.device))
+            for _ in range(4):
+                buffers.append(_backend.DeviceBuffer(4 * n_pairs * k, buffer.device))
+            if return_curves:
+                for _ in range(3):
+                    buffers.append(_backend.DeviceBuffer(4 * total, buffer.device))
+            index_pairs = pairs + np.array([0, n_queries], dtype=np.int32)   # (the targets lie behind the queries)
+            _backend.dtw_detect(buffer.ptr, dim, first, count, index_pairs, metric, normalized, k, max_score,
+                                *[b.ptr for b in buffers[:5]],
+                                **(dict(curve_first=curve_first[:-1], d_curve_cost=buffers[5].ptr,
+                                        d_curve_len=buffers[6].ptr, d_curve_start=buffers[7].ptr)
+                                   if return_curves else {}),
+                                device=buffer.device)
+            if top_k is None:
+                for b, out in zip(buffers, (counts, cost, length, start, end) + (curves[1:] if return_curves else ())):
+                    b.download(out)
+            else:
+                # the pairs grouped by query, in the caller's order within a query; the detections stay where they are
+                order = np.argsort(pairs[:, 0], kind='stable').astype(np.int32)
+                bounds = np.concatenate([[0], np.cumsum(np.bincount(pairs[:, 0], minlength=n_queries))])
+                best = [_backend.DeviceBuffer(4 * n_queries, buffer.device)]
+                buffers.append(best[0])
+                for _ in range(6):
+                    best.append(_backend.DeviceBuffer(4 * n_queries * slots, buffer.device))
+                    buffers.append(best[-1])
+                _backend.dtw_topk(*[b.ptr for b in buffers[:5]], n_pairs, k, normalized, order, bounds, slots,
+                                  *[b.ptr for b in best], device=buffer.device)
+                for b, out in zip(best, (counts, top_pair, top_rank, cost, length, start, end)):
+                    b.download(out)
+        finally:
+            for b in buffers:
+                b.free()
+            if owned is not None:
+                owned.release()
+    # the rows: the first counts[g] slots of every group
+    slot = np.tile(np.arange(slots, dtype=np.int32), groups)
+    keep = np.flatnonzero(slot < np.repeat(counts, slots))
+    group = (keep // slots).astype(np.int32)
+    if top_k is None:
+        pair, rank = group, slot[keep]
+    else:
+        pair, rank = top_pair[keep], top_rank[keep]
+    cost, length, start, end = cost[keep], length[keep], start[keep], end[keep]
+    score = cost / length.astype(np.float32) if normalized and keep.size else cost.copy()
+    target = pairs[pair, 1] if keep.size else np.zeros(0, dtype=np.int32)
+    onset, offset = _times(features, where, target, start, end)
+    return DtwDetections(pair, pairs[pair, 0] if keep.size else target, target, rank, score, cost, length, start,
+                         end, onset, offset, counts, curves, top_k)
