@@ -829,6 +829,44 @@ int snf_dtw_topk(int device_id, const int32_t* d_count, const float* d_cost, con
                  int32_t top_k, int32_t* d_top_count, int32_t* d_top_pair, int32_t* d_top_rank, float* d_top_cost,
                  int32_t* d_top_len, int32_t* d_top_start, int32_t* d_top_end, void* stream);
 
+/* ---- Warping paths: the alignment itself, of DTW pairs and of search hits ----------------------------------------
+ * An extension with no reference call behind it, on top of snf_dtw_pairs and snf_dtw_detect: the frame-to-frame map
+ * that their cost, length, start and end summarise.  The definition is this project's own (DESIGN 4.19,
+ * tests/dtw_align_f64.py); agreement with any outside toolkit is unpinned.
+ *
+ * Items, pairs, `metric`, streams and slots are those of snf_dtw_pairs.  Every cell of the lattice keeps its decision
+ * K: 0 for (i-1, j-1), 1 for (i-1, j), 2 for (i, j-1) - the predecessor that the lattice takes anyway, smallest C,
+ * ties to the first of that order - and 3 for an origin.  The path of an end (N-1, e) follows K back to an origin and
+ * is listed forward as frames (i, j), counted from the first row of each item; it has exactly L[N-1][e] cells.
+ * `mode`:
+ *   SNF_DTW_ALIGN_GLOBAL: the lattice of snf_dtw_pairs, d_cost [P] and d_len [P] as it writes them; one path per
+ *   pair, from (0, 0) to (N-1, M-1).  K = 1 slot per pair; normalized, max_detections, max_score, d_count, d_start
+ *   and d_end are not looked at.
+ *   SNF_DTW_ALIGN_SUBSEQUENCE: the lattice and the detections of snf_dtw_detect with K = `max_detections` slots per
+ *   pair, d_count [P] and d_cost, d_len, d_start, d_end [P K] as it writes them (no curves; K = 1 with max_score
+ *   +inf is the match of snf_dtw_search); one path per detection, from (0, d_start) to (N-1, d_end).
+ * Cost, length, start and end are bit for bit what the sibling calls return for the same tables.
+ * Paths: h_path_first is a HOST array of P K element offsets.  Slot p K + r owns the N + M - 1 elements from
+ * h_path_first[p K + r] of d_path_x and d_path_y (the longest path there can be); cell c < L of its path goes to
+ * element h_path_first[p K + r] + c: the query's (x's) frame to d_path_x, the target's (y's) to d_path_y.  Exactly
+ * the first L elements of a slot with a detection are written, nothing else in the two arrays is touched.
+ * Scratch: the lattice leaves 16 bytes per step of every strip of 64 rows, 16 (N + ceil(N / 64) (M - 1)) bytes a pair
+ * (29 KB for 298 x 298, 4.3 MB for 4096 x 4096), in a buffer of at most `scratch_bytes` (0: 1 GiB) that the slot
+ * keeps; the pairs are worked in as many runs (a lattice launch per class and a traceback launch each, on the
+ * stream) as that takes.  Non-finite features give undefined values and paths, nothing worse.
+ * SNF_E_INVALID, before any device work: what snf_dtw_pairs (subsequence: snf_dtw_detect) refuses, an unknown mode,
+ * a null path table or misaligned path array, a path stretch below element 0, ending beyond element 2^31 or
+ * overlapping another's, a negative scratch_bytes or one below the records of the largest pair of the call.
+ * n_pairs = 0 does nothing. */
+#define SNF_DTW_ALIGN_GLOBAL 0
+#define SNF_DTW_ALIGN_SUBSEQUENCE 1
+int snf_dtw_align(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                  const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
+                  int32_t metric, int32_t mode, int32_t normalized, int32_t max_detections, float max_score,
+                  int32_t* d_count, float* d_cost, int32_t* d_len, int32_t* d_start, int32_t* d_end,
+                  const int64_t* h_path_first, int32_t* d_path_x, int32_t* d_path_y, int64_t scratch_bytes,
+                  void* stream);
+
 /* ---- ABX triplet counts over a table of distances (the two steps after the distances in the reference's examples) --
  * An extension with no reference call behind it: the reference's examples run `abx-score` and `abx-analyze` of an
  * external toolkit on the CPU (reference examples/features_abx/scripts/abx_score.sh:22-23), one triplet at a time,

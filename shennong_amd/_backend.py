@@ -50,6 +50,7 @@ EXPORTS = [
     'snf_crepe_forward_bf16', 'snf_resample_num_out', 'snf_linear_resample', 'snf_crepe_rows',
     'snf_crepe_voicing_convert', 'snf_bottleneck_extract', 'snf_bottleneck_extract_runs',
     'snf_collate_num_out', 'snf_collate_padded', 'snf_dtw_pairs', 'snf_dtw_search', 'snf_dtw_detect', 'snf_dtw_topk',
+    'snf_dtw_align',
     'snf_abx_cells']
 
 
@@ -213,6 +214,8 @@ def lib():
                                      pi64, vp, vp, vp, vp]
         L.snf_dtw_topk.argtypes = [i32, vp, vp, vp, vp, vp, i64, i32, i32, pi32, pi64, i64, i32, vp, vp, vp, vp, vp,
                                    vp, vp, vp]
+        L.snf_dtw_align.argtypes = [i32, vp, i32, pi64, pi32, i64, pi32, i64, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp,
+                                    pi64, vp, vp, i64, vp]
         L.snf_abx_cells.argtypes = [i32, vp, vp, i64, pi64, i64, vp, vp]
         # the library's own allocations (plan scratch: ~19 GB for a 10 000-utterance pitch batch) reclaim
         # what DEVICE_POOL has parked before they give up
@@ -1146,6 +1149,49 @@ def dtw_topk(d_count, d_cost, d_len, d_start, d_end, n_pairs, max_detections, no
         group_first.shape[0] - 1, int(top_k), C.c_void_p(d_top_count), C.c_void_p(d_top_pair),
         C.c_void_p(d_top_rank), C.c_void_p(d_top_cost), C.c_void_p(d_top_len), C.c_void_p(d_top_start),
         C.c_void_p(d_top_end), C.c_void_p(stream) if stream else None))
+
+
+DTW_ALIGN_MODES = {'global': 0, 'subsequence': 1}   # SNF_DTW_ALIGN_GLOBAL, SNF_DTW_ALIGN_SUBSEQUENCE
+
+
+def dtw_record_bytes(n, m):
+    """Bytes of decision records that ``dtw_align`` keeps for a lattice of `n` rows and `m` columns (arrays too):
+    16 per step of every strip of 64 rows"""
+    n, m = np.asarray(n, dtype=np.int64), np.asarray(m, dtype=np.int64)
+    return 16 * (n + ((n + 63) // 64) * (m - 1))
+
+
+def dtw_align(d_rows, dim, item_first, item_count, pairs, metric, mode, d_cost, d_len, path_first, d_path_x,
+              d_path_y, normalized=True, max_detections=1, max_score=None, d_count=None, d_start=None, d_end=None,
+              scratch_bytes=0, device=None, stream=None):
+    """The warping paths of every pair of `pairs` [P, 2] over the items of ``dtw_pairs``.  `mode` 'global': cost and
+    length as ``dtw_pairs``, one path per pair; 'subsequence': count, cost, length, start and end as ``dtw_detect``
+    with `max_detections` slots per pair, one path per detection.  `path_first` (host int64 [P * slots], element
+    offsets): the frames of the cells of a slot's path go to `d_path_x` and `d_path_y` (int32) from its offset, each
+    slot owning N + M - 1 elements.  See snf_dtw_align in include/shennong_amd.h"""
+    first = np.ascontiguousarray(item_first, dtype=np.int64)
+    count = np.ascontiguousarray(item_count, dtype=np.int32)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    if metric not in DTW_METRICS:
+        raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(DTW_METRICS)))
+    if mode not in DTW_ALIGN_MODES:
+        raise ValueError('invalid mode "{}", choose in "{}"'.format(mode, ', '.join(DTW_ALIGN_MODES)))
+    slots = int(max_detections) if mode == 'subsequence' else 1
+    path_first = np.ascontiguousarray(path_first, dtype=np.int64).reshape(-1)
+    if path_first.shape[0] != pairs.shape[0] * slots:
+        raise ValueError('path_first has {} entries for {} pairs of {} slots'.format(
+            path_first.shape[0], pairs.shape[0], slots))
+    if path_first.shape[0] == 0:   # (ctypes gives no address of an empty array)
+        path_first = np.zeros(1, dtype=np.int64)
+    pointer = lambda d: C.c_void_p(d) if d else None   # noqa: E731
+    check(lib().snf_dtw_align(
+        _DEVICE if device is None else int(device), C.c_void_p(d_rows), int(dim),
+        first.ctypes.data_as(C.POINTER(C.c_int64)), count.ctypes.data_as(C.POINTER(C.c_int32)), first.shape[0],
+        pairs.ctypes.data_as(C.POINTER(C.c_int32)), pairs.shape[0], DTW_METRICS[metric], DTW_ALIGN_MODES[mode],
+        int(bool(normalized)), int(max_detections), float('inf') if max_score is None else float(max_score),
+        pointer(d_count), C.c_void_p(d_cost), C.c_void_p(d_len), pointer(d_start), pointer(d_end),
+        path_first.ctypes.data_as(C.POINTER(C.c_int64)), C.c_void_p(d_path_x), C.c_void_p(d_path_y),
+        int(scratch_bytes), C.c_void_p(stream) if stream else None))
 
 
 def abx_cells(d_cost, d_len, n_dist, cells, d_counts, device=None, stream=None):

@@ -21,6 +21,7 @@ namespace {
 struct DtwSlot {
   int device = -1;
   DevBuf items, pairs, aux, curves;   // (curves: the curve offsets of a search, in the caller's pair order)
+  DevBuf record_first, records;       // (snf_dtw_align: the first record of every sorted pair; the records)
   hipEvent_t done = nullptr;
   bool taken = false;   // between take_slot and the event's record (or the failure that gives it back)
 };
@@ -135,12 +136,25 @@ int sort_pairs(const std::string& who, DtwTables& t) {
   return SNF_OK;
 }
 
-// Takes a slot, uploads the tables (and `curve_first`, the curve offsets of a search, where given), sizes the aux
+// The records of an alignment are bounded by the caller's scratch_bytes: no head-room, as DevBuf::ensure adds
+int ensure_exactly(DevBuf& buf, size_t bytes) {
+  if (bytes <= buf.cap) return SNF_OK;
+  if (buf.p) (void)hipFree(buf.p);
+  buf.p = nullptr;
+  buf.cap = 0;
+  SNF_HIP_CHECK(malloc_with_hook(&buf.p, bytes));
+  buf.cap = bytes;
+  return SNF_OK;
+}
+
+// Takes a slot, uploads the tables (and `curve_first`, the curve offsets of a search or the path offsets of an
+// alignment, where given; `record_first` and `record_bytes` of records, where given: snf_dtw_align), sizes the aux
 // block and calls `launch(slot, compute_units, stream)`, which enqueues the kernels; records the slot's event behind
 // them
 template <class Launch>
 int enqueue(const std::string& who, int device_id, void* stream, const DtwTables& t, int32_t dim, int32_t metric,
-            const std::vector<int64_t>* curve_first, Launch&& launch) {
+            const std::vector<int64_t>* curve_first, const std::vector<int64_t>* record_first, size_t record_bytes,
+            Launch&& launch) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return set_error(SNF_E_NODEVICE, "no HIP device visible: libshennong_hip needs an MI355X (gfx950)");
@@ -159,6 +173,8 @@ int enqueue(const std::string& who, int device_id, void* stream, const DtwTables
   int rc = slot->items.upload(t.items, mine->stream);
   if (!rc) rc = slot->pairs.upload(t.pairs, mine->stream);
   if (!rc && curve_first) rc = slot->curves.upload(*curve_first, mine->stream);
+  if (!rc && record_first) rc = slot->record_first.upload(*record_first, mine->stream);
+  if (!rc && record_bytes) rc = ensure_exactly(slot->records, record_bytes);
   // (symkl: the log block of the row range too; a failed allocation ends the call before any kernel)
   if (!rc) rc = slot->aux.ensure(sizeof(float) * dtw_aux_floats(t.row_hi - t.row_lo, dim, metric));
   if (!rc) rc = launch(*slot, compute_units, s);
@@ -220,7 +236,7 @@ int snf_dtw_pairs(int device_id, const float* d_rows, int32_t dim, const int64_t
   if (bad_word_pointer(d_cost) || bad_word_pointer(d_len))
     return set_error(SNF_E_INVALID, "dtw: d_cost or d_len is null or not 4-byte aligned");
   if (const int rc = sort_pairs(who, t)) return rc;
-  return enqueue(who, device_id, stream, t, dim, metric, nullptr, [&](DtwSlot& slot, int compute_units, hipStream_t s) {
+  return enqueue(who, device_id, stream, t, dim, metric, nullptr, nullptr, 0, [&](DtwSlot& slot, int compute_units, hipStream_t s) {
     return launch_dtw_pairs(d_rows, dim, slot.items.as<DtwItem>(), slot.pairs.as<DtwPair>(), t.class_count, t.row_lo,
                             t.row_hi, slot.aux.as<float>(), metric, compute_units, d_cost, d_len, s);
   });
@@ -251,7 +267,7 @@ int snf_dtw_search(int device_id, const float* d_rows, int32_t dim, const int64_
                                     curve_first))
       return rc;
   if (const int rc = sort_pairs(who, t)) return rc;
-  return enqueue(who, device_id, stream, t, dim, metric, curve_pointers ? &curve_first : nullptr,
+  return enqueue(who, device_id, stream, t, dim, metric, curve_pointers ? &curve_first : nullptr, nullptr, 0,
                  [&](DtwSlot& slot, int compute_units, hipStream_t s) {
                    const DtwSearchOut out = {d_cost, d_len, d_start, d_end,
                                              curve_pointers ? slot.curves.as<int64_t>() : nullptr,
@@ -293,7 +309,7 @@ int snf_dtw_detect(int device_id, const float* d_rows, int32_t dim, const int64_
                                     curve_first))
       return rc;
   if (const int rc = sort_pairs(who, t)) return rc;
-  return enqueue(who, device_id, stream, t, dim, metric, curve_pointers ? &curve_first : nullptr,
+  return enqueue(who, device_id, stream, t, dim, metric, curve_pointers ? &curve_first : nullptr, nullptr, 0,
                  [&](DtwSlot& slot, int compute_units, hipStream_t s) {
                    const DtwDetectOut out = {d_count, d_cost, d_len, d_start, d_end, max_detections, max_score,
                                              curve_pointers ? slot.curves.as<int64_t>() : nullptr,
@@ -302,6 +318,115 @@ int snf_dtw_detect(int device_id, const float* d_rows, int32_t dim, const int64_
                                             t.class_count, t.row_lo, t.row_hi, slot.aux.as<float>(), metric,
                                             normalized, compute_units, out, s);
                  });
+}
+
+int snf_dtw_align(int device_id, const float* d_rows, int32_t dim, const int64_t* h_item_first,
+                  const int32_t* h_item_count, int64_t n_items, const int32_t* h_pairs, int64_t n_pairs,
+                  int32_t metric, int32_t mode, int32_t normalized, int32_t max_detections, float max_score,
+                  int32_t* d_count, float* d_cost, int32_t* d_len, int32_t* d_start, int32_t* d_end,
+                  const int64_t* h_path_first, int32_t* d_path_x, int32_t* d_path_y, int64_t scratch_bytes,
+                  void* stream) {
+  const std::string who = "dtw_align";
+  DtwTables t;
+  if (const int rc = check_tables(who, dim, metric, h_item_first, h_item_count, n_items, h_pairs, n_pairs, t))
+    return rc;
+  if (mode != SNF_DTW_ALIGN_GLOBAL && mode != SNF_DTW_ALIGN_SUBSEQUENCE)
+    return set_error(SNF_E_INVALID, who + ": mode must be 0 (global) or 1 (subsequence), not " + std::to_string(mode));
+  const bool subsequence = mode == SNF_DTW_ALIGN_SUBSEQUENCE;
+  if (subsequence) {
+    if (normalized != 0 && normalized != 1) return set_error(SNF_E_INVALID, who + ": normalized must be 0 or 1");
+    if (max_detections < 1 || max_detections > kDtwMaxDetections)
+      return set_error(SNF_E_INVALID, who + ": max_detections must be in [1, " + std::to_string(kDtwMaxDetections) +
+                                          "], not " + std::to_string(max_detections));
+    if (max_score != max_score) return set_error(SNF_E_INVALID, who + ": max_score is not a number");
+  }
+  if (scratch_bytes < 0) return set_error(SNF_E_INVALID, who + ": scratch_bytes is negative");
+  if (n_pairs == 0) return SNF_OK;
+  const int64_t k = subsequence ? max_detections : 1;
+  if (bad_word_pointer(d_rows))
+    return set_error(SNF_E_INVALID, who + ": d_rows is null or not aligned to float32");
+  if (bad_word_pointer(d_cost) || bad_word_pointer(d_len))
+    return set_error(SNF_E_INVALID, who + ": d_cost or d_len is null or not 4-byte aligned");
+  if (subsequence && (bad_word_pointer(d_count) || bad_word_pointer(d_start) || bad_word_pointer(d_end)))
+    return set_error(SNF_E_INVALID, who + ": d_count, d_start or d_end is null or not 4-byte aligned");
+  if (!h_path_first) return set_error(SNF_E_INVALID, who + ": null path table");
+  if (bad_word_pointer(d_path_x) || bad_word_pointer(d_path_y))
+    return set_error(SNF_E_INVALID, who + ": d_path_x or d_path_y is null or not 4-byte aligned");
+  // the paths: slot p k + r owns [first, first + N + M - 1), inside [0, 2^31), and no two overlap
+  std::vector<int64_t> path_first(h_path_first, h_path_first + n_pairs * k);
+  {
+    auto room = [&](int64_t slot) {
+      const int64_t p = slot / k;
+      return int64_t(t.items[h_pairs[2 * p]].frames) + t.items[h_pairs[2 * p + 1]].frames - 1;
+    };
+    std::vector<std::pair<int64_t, int64_t>> stretch(path_first.size());   // (first, slot)
+    bool ascending = true;   // (one stretch behind the other in the order of the slots: nothing to sort)
+    for (int64_t s = 0; s < n_pairs * k; ++s) {
+      if (s > 0 && path_first[s - 1] + room(s - 1) > path_first[s]) ascending = false;
+      if (path_first[s] < 0 || path_first[s] + room(s) > (int64_t(1) << 31))
+        return set_error(SNF_E_INVALID, who + ": the path of pair " + std::to_string(s / k) + ", slot " +
+                                            std::to_string(s % k) + " (" + std::to_string(room(s)) + " elements at " +
+                                            std::to_string(path_first[s]) + ") lies outside [0, 2^31)");
+      stretch[s] = {path_first[s], s};
+    }
+    if (!ascending) std::sort(stretch.begin(), stretch.end());
+    for (size_t s = 0; !ascending && s + 1 < stretch.size(); ++s)
+      if (stretch[s].first + room(stretch[s].second) > stretch[s + 1].first) {
+        const int64_t a = std::min(stretch[s].second, stretch[s + 1].second);
+        const int64_t b = std::max(stretch[s].second, stretch[s + 1].second);
+        return set_error(SNF_E_INVALID, who + ": the paths of pair " + std::to_string(a / k) + ", slot " +
+                                            std::to_string(a % k) + " and pair " + std::to_string(b / k) + ", slot " +
+                                            std::to_string(b % k) + " overlap");
+      }
+  }
+  if (const int rc = sort_pairs(who, t)) return rc;
+  // The records: the sorted pairs are walked in runs whose records fit the scratch; `record_first` counts from the
+  // start of a pair's run
+  const int64_t scratch = scratch_bytes ? scratch_bytes : kDtwDefaultScratch;
+  std::vector<int64_t> record_first(t.pairs.size());
+  std::vector<int64_t> run_first = {0};   // the first pair of every run, and P
+  int64_t largest = 0, fill = 0, most = 0;
+  for (size_t p = 0; p < t.pairs.size(); ++p) {
+    const int64_t need = dtw_record_count(t.items[t.pairs[p].x].frames, t.items[t.pairs[p].y].frames);
+    largest = std::max(largest, need);
+    if ((fill + need) * kDtwRecordBytes > scratch && fill > 0) {
+      run_first.push_back(static_cast<int64_t>(p));
+      fill = 0;
+    }
+    record_first[p] = fill;
+    fill += need;
+    most = std::max(most, fill);
+  }
+  run_first.push_back(n_pairs);
+  if (largest * kDtwRecordBytes > scratch)
+    return set_error(SNF_E_INVALID, who + ": scratch_bytes " + std::to_string(scratch) + " is below the " +
+                                        std::to_string(largest * kDtwRecordBytes) +
+                                        " bytes of records of the largest pair");
+  return enqueue(
+      who, device_id, stream, t, dim, metric, &path_first, &record_first, static_cast<size_t>(most * kDtwRecordBytes),
+      [&](DtwSlot& slot, int compute_units, hipStream_t s) {
+        if (const int rc = launch_dtw_rows(d_rows, dim, t.row_lo, t.row_hi, slot.aux.as<float>(), metric, s))
+          return rc;
+        const DtwDetectOut out = {d_count,   d_cost, d_len,   d_start, d_end, static_cast<int32_t>(k),
+                                  max_score, nullptr, nullptr, nullptr, nullptr};
+        const DtwPaths paths = {slot.curves.as<int64_t>(), d_path_x, d_path_y};
+        for (size_t r = 0; r + 1 < run_first.size(); ++r) {
+          // the pairs [lo, hi) of the run, by class: the classes lie one behind the other in the sorted pairs
+          const int64_t lo = run_first[r], hi = run_first[r + 1];
+          int64_t run_count[kDtwClasses], class_lo = 0;
+          for (int c = 0; c < kDtwClasses; ++c) {
+            const int64_t class_hi = class_lo + t.class_count[c];
+            run_count[c] = std::max<int64_t>(std::min(hi, class_hi) - std::max(lo, class_lo), 0);
+            class_lo = class_hi;
+          }
+          const DtwRecords records = {slot.records.as<uint4>(), slot.record_first.as<int64_t>() + lo};
+          if (const int rc = launch_dtw_align(d_rows, dim, slot.items.as<DtwItem>(), slot.pairs.as<DtwPair>() + lo,
+                                              run_count, t.row_lo, slot.aux.as<float>(), metric, subsequence,
+                                              normalized, compute_units, out, records, paths, s))
+            return rc;
+        }
+        return static_cast<int>(SNF_OK);
+      });
 }
 
 int snf_dtw_topk(int device_id, const int32_t* d_count, const float* d_cost, const int32_t* d_len,

@@ -4,7 +4,10 @@
 // down by DPP, as described at the top of kernels_dtw_search.hip - and, once (C, W)[N - 1][j] of every end j < M lies
 // in the seam row, the tail that `OUT` asks for: the one best end (DtwSearchOut) or up to k detections (DtwDetectOut,
 // described at the top of kernels_dtw_detect.hip).  The search keeps its text, so that its kernels compile to what
-// they were.
+// they were.  pair_strips is the body of dtw_pairs_kernel (kernels_dtw.hip) in the same way.  Both take a
+// record policy: with DtwRecords (pair_strips) or DtwAlignOut (search_pairs: the detections' tail) the lattice also
+// leaves the decision of every cell for the traceback of snf_dtw_align (kernels_dtw_align.hip); with the
+// siblings' policies none of that is compiled.
 #pragma once
 #include <type_traits>
 
@@ -13,11 +16,128 @@
 namespace snf {
 namespace {
 
+// The record of step t of a strip (snf_dtw_align; the layout: the top of kernels_dtw_align.hip): lane l brings `k`,
+// the decision of its cell (s0 + l, t - l), 0 where it has none; the two ballots are the two bits of the 64 decisions,
+// and lane 0 stores them as one 16-byte word
+__device__ __forceinline__ void store_record(uint4* __restrict__ at, const int k, const int lane) {
+  const unsigned long long b0 = __ballot(k & 1), b1 = __ballot(k & 2);
+  if (lane == 0)
+    *at = make_uint4(static_cast<unsigned>(b0), static_cast<unsigned>(b0 >> 32), static_cast<unsigned>(b1),
+                     static_cast<unsigned>(b1 >> 32));
+}
+
+// The body of dtw_pairs_kernel (kernels_dtw.hip, which describes it) and, with REC = DtwRecords, of the global
+// lattice of snf_dtw_align, which also leaves the decision of every cell: 0 (i-1, j-1), 1 (i-1, j), 2 (i, j-1),
+// 3 the origin.  With DtwNoRecords nothing of that is compiled.
+template <int METRIC, int SLOTS, int SEAM, class REC>
+__device__ __forceinline__ void pair_strips(const float* __restrict__ rows, const int dim,
+                                            const DtwItem* __restrict__ items, const DtwPair* __restrict__ pairs,
+                                            const int64_t n_pairs, const float* __restrict__ aux,
+                                            const int64_t row_lo, float* __restrict__ cost,
+                                            int32_t* __restrict__ len, const REC records) {
+  constexpr bool kRec = std::is_same<REC, DtwRecords>::value;
+  constexpr int S = 32 * SLOTS;
+  __shared__ float ring[64 * S];
+  __shared__ float xa[64];
+  __shared__ float2 seam[SEAM];
+  const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
+  const float inf = __builtin_inff();
+  for (int64_t p = blockIdx.x; p < n_pairs; p += gridDim.x) {
+    const DtwPair pair = pairs[p];
+    const DtwItem ix = items[pair.x], iy = items[pair.y];
+    const int N = ix.frames, M = iy.frames;   // (1 <= N <= kDtwMaxFrames, 1 <= M <= SEAM: the host has checked)
+    const float* X = rows + ix.row0 * dim;
+    const float* Y = rows + iy.row0 * dim;
+    // one float of aux per row; symkl: dim + 1, h(row) and behind it the row's logarithms (dtw_log_rows_kernel)
+    const int64_t as = METRIC == SNF_DTW_SYMKL ? dim + 1 : 1;
+    const float* ax = aux + (ix.row0 - row_lo) * as;
+    const float* ay = aux + (iy.row0 - row_lo) * as;
+    uint4* rec = nullptr;   // the record of step 0 of the strip in hand
+    if constexpr (kRec) rec = records.rec + records.first[p];
+    float C = 0.0f;
+    int L = 0;
+    for (int s0 = 0; s0 < N; s0 += 64) {
+      const int R = min(64, N - s0);
+      const bool more = s0 + 64 < N;
+      __syncthreads();   // (the last strip's reads of xa are done)
+      xa[lane] = ax[min(s0 + lane, N - 1) * as];
+      __syncthreads();
+      const float* x0 = X + static_cast<int64_t>(min(s0 + li, N - 1)) * dim;
+      const float* x1 = X + static_cast<int64_t>(min(s0 + 32 + li, N - 1)) * dim;
+      const float *lx0 = nullptr, *lx1 = nullptr;
+      if constexpr (METRIC == SNF_DTW_SYMKL) {
+        lx0 = ax + 1 + min(s0 + li, N - 1) * as;
+        lx1 = ax + 1 + min(s0 + 32 + li, N - 1) * as;
+      }
+      float dgC = inf;   // (C, L) of cell (i - 1, j - 1): what came from lane i - 1 one step earlier
+      int dgL = 0;
+      int pos = -lane;   // (t - lane) mod S once t >= lane
+      int slot = 0;      // (t / 32) mod SLOTS
+      const int steps = R + M - 1;
+      for (int t = 0; t < steps; ++t) {
+        if ((t & 31) == 0 && t < M) {   // (the same for the whole wave)
+          const int col = min(t + li, M - 1);
+          const float* yc = Y + static_cast<int64_t>(col) * dim;
+          const float ya = ay[col * as];
+          const float* lyc = nullptr;
+          if constexpr (METRIC == SNF_DTW_SYMKL) lyc = ay + 1 + col * as;
+          make_tile<METRIC, S>(x0, x1, yc, lx0, lx1, lyc, dim, R > 32, lh, li, 32 * slot, ya, xa, ring);
+          slot = slot + 1 == SLOTS ? 0 : slot + 1;
+          __syncthreads();
+        }
+        float upC = __builtin_bit_cast(float, from_lane_below(__builtin_bit_cast(int, C)));
+        int upL = from_lane_below(L);
+        if (lane == 0) {
+          upC = inf;
+          upL = 0;
+          if (s0 > 0 && t < M) {
+            const float2 above = seam[t];
+            upC = above.x;
+            upL = __builtin_bit_cast(int, above.y);
+          }
+        }
+        const int j = t - lane;
+        int made = 0;   // (kRec: the decision of this lane's cell)
+        if (j >= 0 && j < M && lane < R) {
+          const float d = ring[lane * S + pos];
+          float bestC = j > 0 ? dgC : inf;
+          int bestL = dgL;
+          if (upC < bestC) {
+            bestC = upC;
+            bestL = upL;
+            if constexpr (kRec) made = 1;
+          }
+          if (j > 0 && C < bestC) {
+            bestC = C;
+            bestL = L;
+            if constexpr (kRec) made = 2;
+          }
+          const bool origin = s0 + lane == 0 && j == 0;
+          C = origin ? d : d + bestC;
+          L = origin ? 1 : bestL + 1;
+          if constexpr (kRec) made = origin ? 3 : made;
+          dgC = upC;
+          dgL = upL;
+          if (more && lane == 63) seam[j] = make_float2(C, __builtin_bit_cast(float, L));
+        }
+        if constexpr (kRec) store_record(rec + t, made, lane);
+        pos = pos + 1 == S ? 0 : pos + 1;
+      }
+      if constexpr (kRec) rec += steps;
+      if (!more && lane == R - 1) {
+        cost[pair.out] = C;
+        len[pair.out] = L;
+      }
+    }
+  }
+}
+
 template <int METRIC, int SLOTS, int SEAM, class OUT>
 __device__ __forceinline__ void search_pairs(const float* __restrict__ rows, const int dim,
                                              const DtwItem* __restrict__ items, const DtwPair* __restrict__ pairs,
                                              const int64_t n_pairs, const float* __restrict__ aux,
                                              const int64_t row_lo, const int normalized, const OUT out) {
+  constexpr bool kRec = std::is_same<OUT, DtwAlignOut>::value;   // (snf_dtw_align: the detections' tail, and records)
   constexpr int S = 32 * SLOTS;
   __shared__ float ring[64 * S];
   __shared__ float xa[64];
@@ -36,6 +156,8 @@ __device__ __forceinline__ void search_pairs(const float* __restrict__ rows, con
     // (the host has checked that [curve, curve + M) lies in [0, 2^31) and overlaps no other pair's stretch)
     const bool curves = out.curve_first != nullptr;
     const int64_t curve = curves ? out.curve_first[pair.out] : 0;
+    uint4* rec = nullptr;   // (kRec: the record of step 0 of the strip in hand, as in pair_strips)
+    if constexpr (kRec) rec = out.records.rec + out.records.first[p];
     float C = 0.0f;
     int W = 0;   // L | B << 16
     for (int s0 = 0; s0 < N; s0 += 64) {
@@ -79,6 +201,7 @@ __device__ __forceinline__ void search_pairs(const float* __restrict__ rows, con
           }
         }
         const int j = t - lane;
+        int made = 0;   // (kRec: the decision of this lane's cell, 3 in the whole of row 0)
         if (j >= 0 && j < M && lane < R) {
           const float d = ring[lane * S + pos];
           float prevC = j > 0 ? dgC : inf;
@@ -86,24 +209,29 @@ __device__ __forceinline__ void search_pairs(const float* __restrict__ rows, con
           if (upC < prevC) {
             prevC = upC;
             prevW = upW;
+            if constexpr (kRec) made = 1;
           }
           if (j > 0 && C < prevC) {
             prevC = C;
             prevW = W;
+            if constexpr (kRec) made = 2;
           }
           const bool origin = s0 + lane == 0;   // (the whole of row 0: the start is free)
           C = origin ? d : d + prevC;
           W = origin ? (1 | (j << 16)) : prevW + 1;
+          if constexpr (kRec) made = origin ? 3 : made;
           dgC = upC;
           dgW = upW;
           // the seam of the next strip; in the last strip the ends, row N - 1 (lane 0 of a strip has read column j
           // at step j, and this write comes at step j + lane, behind that read in the order of the wave)
           if (lane == (more ? 63 : R - 1)) seam[j] = make_float2(C, __builtin_bit_cast(float, W));
         }
+        if constexpr (kRec) store_record(rec + t, made, lane);
         pos = pos + 1 == S ? 0 : pos + 1;
       }
+      if constexpr (kRec) rec += steps;
     }
-    if constexpr (std::is_same<OUT, DtwDetectOut>::value) {
+    if constexpr (std::is_same<OUT, DtwDetectOut>::value || kRec) {
       // Up to k detections (the top of kernels_dtw_detect.hip).  Lane l owns the ends j = l, l + 64, ...: a round is
       // one pass over them - those that the detection of the round before overlaps die (L = 0 in their seam word),
       // the others are ranked as the search ranks them - and the search's butterfly.  The curves go out first.

@@ -37,8 +37,9 @@
 //     strip reads column t at step t, 63 steps before lane 63 overwrites it - in place.
 // Three instances by the columns of a pair (LDS per wave): M <= 32 (8.5 KB), M <= 512 (28.3 KB), M <= 4096 (56.3 KB).
 // The tile code (frame_distance, from_lane_below, tile_chain, make_tile) lies in dtw_tiles.h: the search kernel
-// (kernels_dtw_search.hip) uses the same.
-#include "dtw_tiles.h"
+// (kernels_dtw_search.hip) uses the same.  The body of the main kernel is pair_strips of dtw_strips.h, which the
+// global lattice of snf_dtw_align (kernels_dtw_align.hip) shares: there it also records the decision of every cell.
+#include "dtw_strips.h"
 
 namespace snf {
 
@@ -86,92 +87,7 @@ __global__ __launch_bounds__(64) void dtw_pairs_kernel(const float* __restrict__
                                                        const DtwPair* __restrict__ pairs, const int64_t n_pairs,
                                                        const float* __restrict__ aux, const int64_t row_lo,
                                                        float* __restrict__ cost, int32_t* __restrict__ len) {
-  constexpr int S = 32 * SLOTS;
-  __shared__ float ring[64 * S];
-  __shared__ float xa[64];
-  __shared__ float2 seam[SEAM];
-  const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
-  const float inf = __builtin_inff();
-  for (int64_t p = blockIdx.x; p < n_pairs; p += gridDim.x) {
-    const DtwPair pair = pairs[p];
-    const DtwItem ix = items[pair.x], iy = items[pair.y];
-    const int N = ix.frames, M = iy.frames;   // (1 <= N <= kDtwMaxFrames, 1 <= M <= SEAM: the host has checked)
-    const float* X = rows + ix.row0 * dim;
-    const float* Y = rows + iy.row0 * dim;
-    // one float of aux per row; symkl: dim + 1, h(row) and behind it the row's logarithms (dtw_log_rows_kernel)
-    const int64_t as = METRIC == SNF_DTW_SYMKL ? dim + 1 : 1;
-    const float* ax = aux + (ix.row0 - row_lo) * as;
-    const float* ay = aux + (iy.row0 - row_lo) * as;
-    float C = 0.0f;
-    int L = 0;
-    for (int s0 = 0; s0 < N; s0 += 64) {
-      const int R = min(64, N - s0);
-      const bool more = s0 + 64 < N;
-      __syncthreads();   // (the last strip's reads of xa are done)
-      xa[lane] = ax[min(s0 + lane, N - 1) * as];
-      __syncthreads();
-      const float* x0 = X + static_cast<int64_t>(min(s0 + li, N - 1)) * dim;
-      const float* x1 = X + static_cast<int64_t>(min(s0 + 32 + li, N - 1)) * dim;
-      const float *lx0 = nullptr, *lx1 = nullptr;
-      if constexpr (METRIC == SNF_DTW_SYMKL) {
-        lx0 = ax + 1 + min(s0 + li, N - 1) * as;
-        lx1 = ax + 1 + min(s0 + 32 + li, N - 1) * as;
-      }
-      float dgC = inf;   // (C, L) of cell (i - 1, j - 1): what came from lane i - 1 one step earlier
-      int dgL = 0;
-      int pos = -lane;   // (t - lane) mod S once t >= lane
-      int slot = 0;      // (t / 32) mod SLOTS
-      const int steps = R + M - 1;
-      for (int t = 0; t < steps; ++t) {
-        if ((t & 31) == 0 && t < M) {   // (the same for the whole wave)
-          const int col = min(t + li, M - 1);
-          const float* yc = Y + static_cast<int64_t>(col) * dim;
-          const float ya = ay[col * as];
-          const float* lyc = nullptr;
-          if constexpr (METRIC == SNF_DTW_SYMKL) lyc = ay + 1 + col * as;
-          make_tile<METRIC, S>(x0, x1, yc, lx0, lx1, lyc, dim, R > 32, lh, li, 32 * slot, ya, xa, ring);
-          slot = slot + 1 == SLOTS ? 0 : slot + 1;
-          __syncthreads();
-        }
-        float upC = __builtin_bit_cast(float, from_lane_below(__builtin_bit_cast(int, C)));
-        int upL = from_lane_below(L);
-        if (lane == 0) {
-          upC = inf;
-          upL = 0;
-          if (s0 > 0 && t < M) {
-            const float2 above = seam[t];
-            upC = above.x;
-            upL = __builtin_bit_cast(int, above.y);
-          }
-        }
-        const int j = t - lane;
-        if (j >= 0 && j < M && lane < R) {
-          const float d = ring[lane * S + pos];
-          float bestC = j > 0 ? dgC : inf;
-          int bestL = dgL;
-          if (upC < bestC) {
-            bestC = upC;
-            bestL = upL;
-          }
-          if (j > 0 && C < bestC) {
-            bestC = C;
-            bestL = L;
-          }
-          const bool origin = s0 + lane == 0 && j == 0;
-          C = origin ? d : d + bestC;
-          L = origin ? 1 : bestL + 1;
-          dgC = upC;
-          dgL = upL;
-          if (more && lane == 63) seam[j] = make_float2(C, __builtin_bit_cast(float, L));
-        }
-        pos = pos + 1 == S ? 0 : pos + 1;
-      }
-      if (!more && lane == R - 1) {
-        cost[pair.out] = C;
-        len[pair.out] = L;
-      }
-    }
-  }
+  pair_strips<METRIC, SLOTS, SEAM>(rows, dim, items, pairs, n_pairs, aux, row_lo, cost, len, DtwNoRecords{});
 }
 
 template <int METRIC, int CLASS>

@@ -488,6 +488,33 @@ struct DtwTopkOut {
 };
 int launch_dtw_topk(const DtwTopkIn& in, int64_t n_queries, int top_k, int normalized, const DtwTopkOut& out,
                     hipStream_t stream);
+// kernels_dtw_align.hip: the warping paths (snf_dtw_align).  The lattices of kernels_dtw.hip and dtw_strips.h, run
+// with a record policy, leave the decision of every cell in `rec` (the layout: the top of kernels_dtw_align.hip), and
+// a traceback kernel behind them on the same stream walks the records back from the ends that the lattice wrote
+struct DtwNoRecords {};          // the record policy of snf_dtw_pairs, snf_dtw_search, snf_dtw_detect: none
+struct DtwRecords {
+  uint4* rec;                    // the records of the pairs of a launch
+  const int64_t* first;          // device: the first record of pair p of the launch (in its sorted order)
+};
+struct DtwAlignOut : DtwDetectOut {   // the subsequence lattice with the detections' tail and records
+  DtwRecords records;
+};
+constexpr int64_t kDtwRecordBytes = 16;
+constexpr int64_t kDtwDefaultScratch = int64_t(1) << 30;
+// records of the lattice of N rows and M columns: every strip of R rows has R + M - 1 steps
+inline int64_t dtw_record_count(int64_t n, int64_t m) { return n + ((n + 63) / 64) * (m - 1); }
+struct DtwPaths {
+  const int64_t* first;          // device [P * k] in the caller's order: slot p * k + r owns [first, first + N + M - 1)
+  int32_t *x, *y;                // the frames of the path's cells, forward
+};
+// One run: `d_pairs` are `run_count[c]` pairs of class c = 0, 1, 2 in this order (a stretch of the sorted pairs),
+// `records.first` their first records.  `d_aux` is written already (launch_dtw_rows).  Global (`subsequence` 0): cost
+// and len [P] as launch_dtw_pairs, one path per pair; else `out` as launch_dtw_detect (no curves), one path per live
+// detection.
+int launch_dtw_align(const float* rows, int dim, const DtwItem* d_items, const DtwPair* d_pairs,
+                     const int64_t* run_count, int64_t row_lo, const float* d_aux, int metric, int subsequence,
+                     int normalized, int compute_units, const DtwDetectOut& out, const DtwRecords& records,
+                     const DtwPaths& paths, hipStream_t stream);
 
 // kernels_abx.hip: ABX triplet counts per cell over a table of distances (snf_abx_cells)
 constexpr int kAbxTile = 1024;        // floats of a B-row staged in LDS at a time (4 KB per wave)

@@ -39,6 +39,16 @@ query over a whole corpus, all picked on the device (snf_dtw_detect, snf_dtw_top
     hits = dtw_detect(feats, queries, targets, max_detections=4, top_k=10)                  # a DtwDetections
     rows = hits.ranked(0)                             # the rows of query 0, the best first
     hits.target[rows], hits.onset[rows], hits.offset[rows]
+
+:func:`dtw_align` returns the alignment itself, the warping path of every pair, walked back on the device from the
+decisions that the lattice takes anyway (snf_dtw_align); ``dtw_search`` and ``dtw_detect`` give
+the paths of their hits with ``return_paths=True``:
+
+    paths = dtw_align(feats, [(0, 1), (0, 2)], items=items)            # a DtwPaths
+    paths.path(0)                                     # int32 [L, 2]: (frame of item 0, frame of item 1) per cell
+    paths.y_range_of_x(0)                             # per frame of item 0 the first and last frame matched to it
+    found = dtw_search(feats, queries, targets, return_paths=True)
+    found.path(best)                                  # (query frame, target frame) of the best match's cells
 """
 
 import numpy as np
@@ -46,7 +56,8 @@ import numpy as np
 from shennong_amd import _backend
 from shennong_amd.device import DeviceFeaturesCollection
 
-__all__ = ['dtw_distances', 'dtw_search', 'dtw_detect', 'DtwMatches', 'DtwDetections', 'MAX_FRAMES']
+__all__ = ['dtw_distances', 'dtw_search', 'dtw_detect', 'dtw_align', 'DtwMatches', 'DtwDetections', 'DtwPaths',
+           'MAX_FRAMES']
 
 MAX_FRAMES = _backend.DTW_MAX_FRAMES
 
@@ -186,6 +197,203 @@ def dtw_distances(features, pairs, items=None, metric='cosine', normalized=True,
     return (distances, lengths) if return_lengths else distances
 
 
+class _PathStore:
+    """The paths of the rows of a result, concatenated: row k owns the elements first[k] .. first[k + 1] of `x` and
+    `y` (int32 frames, counted from the first row of each item).  `centres`: per item the centre times of its rows,
+    `x_item`, `y_item`: the items of every row (or None: no times)"""
+
+    def __init__(self, first, x, y, centres=None, x_item=None, y_item=None):
+        self.first = np.asarray(first, dtype=np.int64)
+        self.x = np.asarray(x, dtype=np.int32)
+        self.y = np.asarray(y, dtype=np.int32)
+        if self.first.ndim != 1 or self.first.shape[0] < 1 or self.first[0] != 0 or (np.diff(self.first) < 0).any():
+            raise ValueError('first must hold ascending offsets [rows + 1] from 0')
+        if self.x.shape != self.y.shape or self.x.ndim != 1 or self.x.shape[0] != self.first[-1]:
+            raise ValueError('x_frame and y_frame must hold the {} frames that first counts'.format(
+                int(self.first[-1])))
+        self.centres, self.x_item, self.y_item = centres, x_item, y_item
+
+    def __len__(self):
+        return self.first.shape[0] - 1
+
+    def bounds(self, k, what):
+        if not -len(self) <= k < len(self):
+            raise IndexError('{} {} is out of range for {}'.format(what, k, len(self)))
+        k = k % len(self)
+        return k, int(self.first[k]), int(self.first[k + 1])
+
+    def path(self, k, what):
+        _, lo, hi = self.bounds(k, what)
+        return np.stack([self.x[lo:hi], self.y[lo:hi]], axis=1)
+
+    def times(self, k, what):
+        if self.centres is None:
+            raise ValueError('no times: the paths were not made from a collection')
+        k, lo, hi = self.bounds(k, what)
+        return np.stack([self.centres[self.x_item[k]][self.x[lo:hi]],
+                         self.centres[self.y_item[k]][self.y[lo:hi]]], axis=1)
+
+
+def _item_centres(features, names, rows, count):
+    """Per item the centre times of its rows: item k is `count[k]` rows of utterance `names[k]` from its row
+    `rows[k]`"""
+    whole = {}
+    for name in set(names):
+        whole[name] = _centres(features[name].times)
+    return [whole[name][lo:lo + n] for name, lo, n in zip(names, rows, count)]
+
+
+def _compact(path_first, length, x, y):
+    """(first [S + 1], x, y): the first length[s] elements from path_first[s] of `x` and `y`, one stretch behind the
+    other"""
+    length = np.asarray(length, dtype=np.int64)
+    first = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+    at = np.repeat(np.asarray(path_first, dtype=np.int64) - first[:-1], length) + np.arange(first[-1])
+    return first, x[at], y[at]
+
+
+def _aligned(buffer, dim, first, count, index_pairs, metric, mode, normalized=True, slots=1, max_score=None,
+             scratch_bytes=0):
+    """One snf_dtw_align over `index_pairs` [P, 2]: (counts [P], cost, length, start, end [P * slots], path_first
+    [P * slots], x, y) on the host; every slot owns N + M - 1 elements of x and y"""
+    n_pairs = index_pairs.shape[0]
+    room = (count[index_pairs[:, 0]].astype(np.int64) + count[index_pairs[:, 1]] - 1).repeat(slots)
+    path_first = np.concatenate([[0], np.cumsum(room)]).astype(np.int64)
+    total = int(path_first[-1])
+    if total >= 2 ** 31:
+        raise ValueError('the paths of the {} pairs need room for {} cells, the limit is 2^31 - 1: align in parts'
+                         .format(n_pairs, total))
+    counts = np.ones(n_pairs, dtype=np.int32)
+    cost = np.zeros(n_pairs * slots, dtype=np.float32)
+    length, start, end = (np.zeros(n_pairs * slots, dtype=np.int32) for _ in range(3))
+    x, y = np.zeros(total, dtype=np.int32), np.zeros(total, dtype=np.int32)
+    buffers = []
+    try:
+        sizes = (n_pairs,) + (n_pairs * slots,) * 4 + (total,) * 2
+        for size in sizes:
+            buffers.append(_backend.DeviceBuffer(4 * max(size, 1), buffer.device))
+        d_count, d_cost, d_len, d_start, d_end, d_x, d_y = (b.ptr for b in buffers)
+        _backend.dtw_align(buffer.ptr, dim, first, count, index_pairs, metric, mode, d_cost, d_len, path_first[:-1],
+                           d_x, d_y, normalized=normalized, max_detections=slots, max_score=max_score,
+                           d_count=d_count, d_start=d_start, d_end=d_end, scratch_bytes=scratch_bytes,
+                           device=buffer.device)
+        outs = (cost, length, x, y) if mode == 'global' else (counts, cost, length, start, end, x, y)
+        which = (1, 2, 5, 6) if mode == 'global' else range(7)
+        for k, out in zip(which, outs):
+            if out.size:
+                buffers[k].download(out)
+    finally:
+        for b in buffers:
+            b.free()
+    return counts, cost, length, start, end, path_first[:-1], x, y
+
+
+class DtwPaths:
+    """The warping paths of a :func:`dtw_align`: numpy columns [P] in the order of the pairs, and the paths
+    concatenated
+
+    `cost` (float32), `length` (int32): C and L of the end cell, as ``dtw_distances`` has them; `distance`
+    (float32): ``cost / length`` if normalized, else the cost.  `first` (int64 [P + 1]): pair p owns the elements
+    first[p] .. first[p + 1] of `x_frame` and `y_frame` (int32), the frames of the cells of its path from (0, 0) to
+    (N-1, M-1), counted from the first row of each item."""
+
+    def __init__(self, cost, length, first, x_frame, y_frame, normalized=True, centres=None, pairs=None):
+        self.cost = np.asarray(cost, dtype=np.float32)
+        self.length = np.asarray(length, dtype=np.int32)
+        if self.cost.ndim != 1 or self.cost.shape != self.length.shape:
+            raise ValueError('cost and length must be one-dimensional and of one length')
+        pairs = None if pairs is None else np.asarray(pairs).reshape(-1, 2)
+        self._store = _PathStore(first, x_frame, y_frame, centres, None if pairs is None else pairs[:, 0],
+                                 None if pairs is None else pairs[:, 1])
+        if len(self._store) != self.cost.shape[0] or (np.diff(self._store.first) != self.length).any():
+            raise ValueError('first must count length[p] cells for every one of the {} pairs'.format(
+                self.cost.shape[0]))
+        self.first, self.x_frame, self.y_frame = self._store.first, self._store.x, self._store.y
+        self.normalized = bool(normalized)
+        self.distance = (self.cost / self.length.astype(np.float32) if self.normalized and len(self)
+                         else self.cost.copy())
+
+    def __len__(self):
+        return self.cost.shape[0]
+
+    def path(self, p):
+        """int32 [L, 2]: (frame of x, frame of y) of every cell of the path of pair `p`, forward"""
+        return self._store.path(p, 'pair')
+
+    def times(self, p):
+        """float64 [L, 2]: the centre times in seconds of the two frames of every cell (the mean of a [n, 2] (start,
+        stop) row of the utterance's times, the value of a [n] one)"""
+        return self._store.times(p, 'pair')
+
+    def y_range_of_x(self, p):
+        """int32 [N, 2]: per frame of x the first and the last frame of y that the path of pair `p` matches to it"""
+        path = self.path(p)
+        x, y = path[:, 0], path[:, 1]
+        turn = np.flatnonzero(np.diff(x))   # (x does not descend and leaves no frame out)
+        return np.stack([y[np.concatenate([[0], turn + 1])], y[np.concatenate([turn, [x.shape[0] - 1]])]],
+                        axis=1).astype(np.int32)
+
+    def save_csv(self, path):
+        """Writes the cells to `path`: a header line ``pair,x_frame,y_frame``, then one line per cell, pair by pair"""
+        pair = np.repeat(np.arange(len(self)), np.diff(self.first))
+        with open(path, 'w') as out:
+            out.write('pair,x_frame,y_frame\n')
+            for row in zip(pair.tolist(), self.x_frame.tolist(), self.y_frame.tolist()):
+                out.write('{},{},{}\n'.format(*row))
+
+
+def dtw_align(features, pairs, items=None, metric='cosine', normalized=True, scratch_bytes=0):
+    """The warping paths of pairs of items of `features` (snf_dtw_align), a :class:`DtwPaths`
+
+    The lattice, `features`, `pairs`, `items`, `metric` and `normalized` are those of :func:`dtw_distances`, and so
+    are cost and length, bit for bit.  Every cell also keeps which predecessor it took - (i-1, j-1), (i-1, j) or
+    (i, j-1): the one of smallest C, ties to the first of that order - and the path of a pair follows these
+    decisions back from (N-1, M-1) to (0, 0); it has exactly `length` cells.  The walk runs on the device, behind
+    the lattice; the definition is this project's own (tests/dtw_align_f64.py states it in float64).
+    `scratch_bytes`: the bound on the device memory that holds the decisions, 16 bytes per step of every strip of 64
+    rows (0: 1 GiB); the pairs are worked in as many runs as that takes.
+
+    ValueError, before any device work: what ``dtw_distances`` raises, paths that need room for 2^31 cells or more,
+    a `scratch_bytes` below the need of the largest pair."""
+    if metric not in _backend.DTW_METRICS:
+        raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(_backend.DTW_METRICS)))
+    if items is None:
+        pairs = [tuple(pair) for pair in pairs]
+    else:
+        items = list(items)
+    given = pairs
+    first, count, pairs, dim, block = _select(features, pairs, items)
+    n_pairs = pairs.shape[0]
+    if not _int_in(scratch_bytes, 0, 2 ** 62):
+        raise ValueError('scratch_bytes must be a non-negative int, not {!r}'.format(scratch_bytes))
+    if n_pairs and scratch_bytes:
+        need = int(_backend.dtw_record_bytes(count[pairs[:, 0]], count[pairs[:, 1]]).max())
+        if scratch_bytes < need:
+            raise ValueError('scratch_bytes {} is below the {} bytes that the largest pair needs'.format(
+                scratch_bytes, need))
+    # the centre times of the rows of every item (items None: the utterances in the order of first appearance)
+    first_of, _, _ = _layout(features)
+    names = (list(dict.fromkeys(name for pair in given for name in pair)) if items is None
+             else [item[0] for item in items])
+    rows = [int(row) - first_of[name] for row, name in zip(first.tolist(), names)]
+    centres = _item_centres(features, names, rows, count.tolist())
+    if not n_pairs:
+        return DtwPaths(np.zeros(0, np.float32), np.zeros(0, np.int32), np.zeros(1, np.int64), np.zeros(0, np.int32),
+                        np.zeros(0, np.int32), normalized, centres, pairs)
+    owned = None
+    if block is None:
+        owned = DeviceFeaturesCollection.from_host(features)
+        block = owned._blocks[0]
+    try:
+        _, cost, length, _, _, path_first, x, y = _aligned(block.alive(), dim, first, count, pairs, metric, 'global',
+                                                           scratch_bytes=scratch_bytes)
+    finally:
+        if owned is not None:
+            owned.release()
+    return DtwPaths(cost, length, *_compact(path_first, length, x, y), normalized=normalized, centres=centres,
+                    pairs=pairs)
+
+
 class DtwMatches:
     """The best match of every (query, target) pair of a :func:`dtw_search`: numpy columns [P] in the order of
     the pairs
@@ -198,7 +406,8 @@ class DtwMatches:
 
     columns = ('query', 'target', 'score', 'cost', 'length', 'start_frame', 'end_frame', 'onset', 'offset')
 
-    def __init__(self, query, target, score, cost, length, start_frame, end_frame, onset, offset, curves=None):
+    def __init__(self, query, target, score, cost, length, start_frame, end_frame, onset, offset, curves=None,
+                 paths=None):
         self.query = np.asarray(query, dtype=np.int32)
         self.target = np.asarray(target, dtype=np.int32)
         self.score = np.asarray(score, dtype=np.float32)
@@ -213,9 +422,25 @@ class DtwMatches:
             raise ValueError('the columns must be one-dimensional and of one length: {}'.format(sorted(sizes)))
         # (first [P + 1], cost, length, start): pair p owns the elements first[p] .. first[p + 1] of the three
         self._curves = curves
+        self._paths = paths   # (a _PathStore with one path per pair, or None)
 
     def __len__(self):
         return self.query.shape[0]
+
+    def path(self, p):
+        """int32 [length, 2]: (query frame, target frame) of every cell of the path of the match of pair `p`, from
+        (0, start_frame) to (N-1, end_frame); the target frames are counted as `start_frame` is.  ValueError when
+        the search did not ask for paths"""
+        if self._paths is None:
+            raise ValueError('no paths: call dtw_search with return_paths=True')
+        return self._paths.path(p, 'pair')
+
+    def times(self, p):
+        """float64 [length, 2]: the centre times in seconds of the query frame and the target frame of every cell of
+        the path of pair `p`"""
+        if self._paths is None:
+            raise ValueError('no paths: call dtw_search with return_paths=True')
+        return self._paths.times(p, 'pair')
 
     def curve(self, p):
         """``(cost [M], length [M], start [M])`` of pair `p`: C, L and B of the path that ends at every frame of the
@@ -305,7 +530,30 @@ def _times(features, where, target, start, end):
     return np.concatenate(begins)[at + start], np.concatenate(ends)[at + end]
 
 
-def dtw_search(features, queries, targets, pairs=None, metric='cosine', normalized=True, return_curves=False):
+def _entry_centres(features, entries, first, count):
+    """Per query and target (`entries`, the queries then the targets) the centre times of its rows"""
+    first_of, _, _ = _layout(features)
+    names = [entry if isinstance(entry, str) else tuple(entry)[0] for entry in entries]
+    rows = [int(row) - first_of[name] for row, name in zip(first.tolist(), names)]
+    return _item_centres(features, names, rows, count.tolist())
+
+
+def _hit_paths(buffer, dim, first, count, index_pairs, metric, normalized, slots, max_score, want, found):
+    """The paths of the detections `want` = (pair [R], rank [R]) by a second pass over their distinct pairs alone
+    (snf_dtw_align, which keeps the decisions of the lattice): (first [R + 1], x, y).  `found` = (length, start, end)
+    [R] of the first pass, which the second must find again"""
+    pair, rank = want
+    distinct, place = np.unique(pair, return_inverse=True)
+    _, _, length, start, end, path_first, x, y = _aligned(buffer, dim, first, count, index_pairs[distinct], metric,
+                                                          'subsequence', normalized, slots, max_score)
+    slot = place.reshape(-1) * slots + rank
+    if not all(np.array_equal(a[slot], b) for a, b in zip((length, start, end), found)):
+        raise RuntimeError('dtw: internal error, the alignment pass found other detections than the search')
+    return _compact(path_first[slot], length[slot], x, y)
+
+
+def dtw_search(features, queries, targets, pairs=None, metric='cosine', normalized=True, return_curves=False,
+               return_paths=False):
     """Query-by-example search: where does every query occur in every target?  Subsequence DTW on the GPU
     (snf_dtw_search), a :class:`DtwMatches` with the best match of every (query, target) pair
 
@@ -331,12 +579,15 @@ def dtw_search(features, queries, targets, pairs=None, metric='cosine', normaliz
     `pairs` None: every query against every target, query-major.  Otherwise an integer array [P, 2] of (query
     index, target index).
     `return_curves`: keep (C, L, B) of every end of every pair for ``DtwMatches.curve``.
+    `return_paths`: keep the warping path of every match for ``DtwMatches.path`` and ``DtwMatches.times``, by a
+    second pass that records the decisions of the lattice (snf_dtw_align; :func:`dtw_align` has the definition).
 
     ValueError, before any device work: an unknown metric, a name that is not in the collection, an index out of
     range, an item without frames or of more than ``MAX_FRAMES`` frames, items of different ndims, a collection in
     several device blocks, curves of 2^31 elements or more."""
     if metric not in _backend.DTW_METRICS:
         raise ValueError('invalid metric "{}", choose in "{}"'.format(metric, ', '.join(_backend.DTW_METRICS)))
+    queries, targets = list(queries), list(targets)
     first, count, pairs, n_queries, where, dim, block = _select_search(features, queries, targets, pairs)
     n_pairs = pairs.shape[0]
     columns = count[n_queries + pairs[:, 1]].astype(np.int64)   # M of every pair
@@ -348,6 +599,7 @@ def dtw_search(features, queries, targets, pairs=None, metric='cosine', normaliz
     cost = np.zeros(n_pairs, dtype=np.float32)
     length, start, end = (np.zeros(n_pairs, dtype=np.int32) for _ in range(3))
     curves = None
+    paths = (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
     if return_curves:
         curves = (curve_first, np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.int32),
                   np.zeros(total, dtype=np.int32))
@@ -373,6 +625,9 @@ def dtw_search(features, queries, targets, pairs=None, metric='cosine', normaliz
                                 device=buffer.device)
             for b, out in zip(buffers, (cost, length, start, end) + (curves[1:] if return_curves else ())):
                 b.download(out)
+            if return_paths:
+                paths = _hit_paths(buffer, dim, first, count, index_pairs, metric, normalized, 1, None,
+                                   (np.arange(n_pairs), np.zeros(n_pairs, dtype=np.int64)), (length, start, end))
         finally:
             for b in buffers:
                 b.free()
@@ -380,7 +635,11 @@ def dtw_search(features, queries, targets, pairs=None, metric='cosine', normaliz
                 owned.release()
     score = cost / length.astype(np.float32) if normalized and n_pairs else cost.copy()
     onset, offset = _times(features, where, pairs[:, 1], start, end)
-    return DtwMatches(pairs[:, 0], pairs[:, 1], score, cost, length, start, end, onset, offset, curves)
+    store = None
+    if return_paths:
+        store = _PathStore(*paths, _entry_centres(features, queries + targets, first, count), pairs[:, 0],
+                           n_queries + pairs[:, 1])
+    return DtwMatches(pairs[:, 0], pairs[:, 1], score, cost, length, start, end, onset, offset, curves, store)
 
 
 class DtwDetections:
@@ -401,7 +660,7 @@ class DtwDetections:
               np.float64, np.float64)
 
     def __init__(self, pair, query, target, rank, score, cost, length, start_frame, end_frame, onset, offset,
-                 counts, curves=None, top_k=None):
+                 counts, curves=None, top_k=None, paths=None):
         given = (pair, query, target, rank, score, cost, length, start_frame, end_frame, onset, offset)
         for name, column, dtype in zip(self.columns, given, self._types):
             setattr(self, name, np.asarray(column, dtype=dtype))
@@ -414,9 +673,24 @@ class DtwDetections:
         self.top_k = top_k
         # (first [P + 1], cost, length, start): pair p owns the elements first[p] .. first[p + 1] of the three
         self._curves = curves
+        self._paths = paths   # (a _PathStore with one path per row, or None)
 
     def __len__(self):
         return self.pair.shape[0]
+
+    def path(self, k):
+        """int32 [length, 2]: (query frame, target frame) of every cell of the path of the detection of row `k`,
+        from (0, start_frame) to (N-1, end_frame).  ValueError when the call did not ask for paths"""
+        if self._paths is None:
+            raise ValueError('no paths: call dtw_detect with return_paths=True')
+        return self._paths.path(k, 'row')
+
+    def times(self, k):
+        """float64 [length, 2]: the centre times in seconds of the query frame and the target frame of every cell of
+        the path of row `k`"""
+        if self._paths is None:
+            raise ValueError('no paths: call dtw_detect with return_paths=True')
+        return self._paths.times(k, 'row')
 
     def of_pair(self, p):
         """The rows of pair `p`, by ascending rank"""
@@ -456,7 +730,7 @@ def _int_in(value, lo, hi):
 
 
 def dtw_detect(features, queries, targets, pairs=None, metric='cosine', normalized=True, max_detections=4,
-               max_score=None, top_k=None, return_curves=False):
+               max_score=None, top_k=None, return_curves=False, return_paths=False):
     """Query-by-example detection: every place a query occurs in a target, not only the best one (snf_dtw_detect), and
     per query the best few over all its targets (snf_dtw_topk); a :class:`DtwDetections`
 
@@ -474,6 +748,8 @@ def dtw_detect(features, queries, targets, pairs=None, metric='cosine', normaliz
 
     `top_k` T: per query only its T best detections, by (score ascending, pair index, rank), are selected on the
     device and downloaded - Q T records instead of P max_detections.
+    `return_paths`: keep the warping path of every row for ``DtwDetections.path`` and ``DtwDetections.times``, by a
+    second pass (snf_dtw_align) over the distinct pairs of the rows alone: with `top_k`, of the surviving detections.
 
     ValueError, before any device work: what ``dtw_search`` raises, `max_detections` not an int in [1, 64], `top_k`
     not an int in [1, 1024], a NaN `max_score`, `top_k` together with `return_curves`."""
@@ -491,6 +767,7 @@ def dtw_detect(features, queries, targets, pairs=None, metric='cosine', normaliz
     if top_k is not None and return_curves:
         raise ValueError('top_k={} with return_curves=True: the curves are per pair, ask for them without top_k'
                          .format(top_k))
+    queries, targets = list(queries), list(targets)
     first, count, pairs, n_queries, where, dim, block = _select_search(features, queries, targets, pairs)
     n_pairs, k = pairs.shape[0], int(max_detections)
     columns = count[n_queries + pairs[:, 1]].astype(np.int64)   # M of every pair
@@ -506,6 +783,7 @@ def dtw_detect(features, queries, targets, pairs=None, metric='cosine', normaliz
     length, start, end = (np.zeros(groups * slots, dtype=np.int32) for _ in range(3))
     top_pair, top_rank = (np.zeros(groups * slots, dtype=np.int32) for _ in range(2))
     curves = None
+    paths = (np.zeros(1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32))
     if return_curves:
         curves = (curve_first, np.zeros(total, dtype=np.float32), np.zeros(total, dtype=np.int32),
                   np.zeros(total, dtype=np.int32))
@@ -546,6 +824,12 @@ def dtw_detect(features, queries, targets, pairs=None, metric='cosine', normaliz
                                   *[b.ptr for b in best], device=buffer.device)
                 for b, out in zip(best, (counts, top_pair, top_rank, cost, length, start, end)):
                     b.download(out)
+            if return_paths:
+                live = np.flatnonzero(np.tile(np.arange(slots), groups) < np.repeat(counts, slots))
+                want = (live // slots, live % slots) if top_k is None else (top_pair[live], top_rank[live])
+                if live.size:
+                    paths = _hit_paths(buffer, dim, first, count, index_pairs, metric, normalized, k, max_score, want,
+                                       (length[live], start[live], end[live]))
         finally:
             for b in buffers:
                 b.free()
@@ -563,5 +847,9 @@ def dtw_detect(features, queries, targets, pairs=None, metric='cosine', normaliz
     score = cost / length.astype(np.float32) if normalized and keep.size else cost.copy()
     target = pairs[pair, 1] if keep.size else np.zeros(0, dtype=np.int32)
     onset, offset = _times(features, where, target, start, end)
+    store = None
+    if return_paths:
+        store = _PathStore(*paths, _entry_centres(features, queries + targets, first, count),
+                           pairs[pair, 0] if keep.size else target, n_queries + target)
     return DtwDetections(pair, pairs[pair, 0] if keep.size else target, target, rank, score, cost, length, start,
-                         end, onset, offset, counts, curves, top_k)
+                         end, onset, offset, counts, curves, top_k, store)
