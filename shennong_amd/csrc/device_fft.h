@@ -10,6 +10,8 @@
 
 #include <cstdint>
 
+#include "utt_search.h"
+
 namespace snf {
 
 namespace {
@@ -267,16 +269,6 @@ __device__ __forceinline__ float row_sum16(float v) {
   v += dpp_row_ror<0x122>(v);  // row_ror:2
   v += dpp_row_ror<0x121>(v);  // row_ror:1
   return v;
-}
-
-__device__ __forceinline__ int64_t find_utt(const int64_t* __restrict__ offsets, int64_t n,
-                                            int64_t g) {
-  int64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (offsets[mid] <= g) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }

@@ -651,7 +651,7 @@ __global__ __launch_bounds__(kMaxWaves * 64, 4) void fbank512_kernel(const Fast5
   if (FUSED) {
     // ---- [cepstra | delta | delta-delta] of the workgroup's frames (DeltaPostProcessor order 2, window
     // 2; [KALDI-UPSTREAM] ComputeDeltas): frame indices clamp at the ends of the utterance, the same
-    // products in the same order as delta_flat_o2w2_kernel (kernels_post.hip) ------------------------
+    // products in the same order as delta_flat_o2w2_kernel (kernels_delta.hip) -----------------------
     __syncthreads();
     const int D = p.num_ceps, OD = 3 * D;
     const int64_t f_first = static_cast<int64_t>(pu_set0) * 4;

@@ -17,6 +17,7 @@
 #include <float.h>
 
 #include "snf_internal.h"
+#include "utt_search.h"
 
 namespace snf {
 
@@ -49,17 +50,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp_f<0x124>(v);
   v += dpp_f<0x128>(v);
   return (lane_f(v, 0) + lane_f(v, 16)) + (lane_f(v, 32) + lane_f(v, 48));
-}
-
-// largest u with offsets[u] <= g (offsets[n] > g): the utterance that owns global row g
-__device__ __forceinline__ int64_t find_utt(const int64_t* __restrict__ offsets, int64_t n,
-                                            int64_t g) {
-  int64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (offsets[mid] <= g) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {

@@ -1,7 +1,8 @@
 """Shapes, frame counts, rows and references for the tests of the PLP tail and RASTA kernels (test_plp_tail.py on the
 CPU, test_plp_tail_gpu.py on the device).  The routing of launch_plp_tail and the block heights of its kernels are
-restated here, not read from the source: a change of kernels_post.hip that moves a route or a seam has to be made
-here too, and `check_frames` / `check_edge_rows` / `check_rasta_layout` then say what the cases no longer reach.
+restated in post_layouts.py, not read from the source: a change of shennong_amd/csrc/post_route.h or
+kernels_plp_tail.hip that moves a route or a seam has to be made there too, and `check_frames` / `check_edge_rows` /
+`check_rasta_layout` then say what the cases no longer reach.
 
 The rows are fed to the tail directly (Plan.debug_plp_tail), so a case measures the tail alone: the float64
 statement (oracle/spec_f64.py plp_tail) and the float32 C oracle (oracle.plp_tail) read the very same float32 rows."""
@@ -12,14 +13,11 @@ import numpy as np
 
 from oracle import oracle as orc
 from oracle import spec_f64
+from post_layouts import (PLP_EXACT_ROWS as EXACT_ROWS, PLP_EXACT_SHAPE as EXACT_SHAPE, PLP_MAX_BINS as MAX_BINS,
+                          PLP_MAX_LPC as MAX_LPC, PLP_REFUSAL as REFUSAL, PLP_SMALL_BINS as SMALL_BINS,
+                          PLP_SMALL_LPC as SMALL_LPC, PLP_SMALL_ROWS as SMALL_ROWS, plp_route_of as route_of)
 from shennong_amd.processor import PlpProcessor
 
-EXACT_ROWS = 256     # frames per workgroup of plp_tail_exact_kernel
-SMALL_ROWS = 64      # ... of plp_tail_small_kernel and plp_tail_kernel
-MAX_BINS, MAX_LPC = 126, 63          # kMaxBins, kMaxLpc
-SMALL_BINS, SMALL_LPC = 32, 16       # the bound of plp_tail_small_kernel<32, 16>
-EXACT_SHAPE = (23, 12, 13)           # (mel bins, LPC order, cepstra) of plp_tail_exact_kernel<23, 12, 13>
-REFUSAL = 'PLP: num_bins > 126 or lpc_order > 63 not supported'
 DURBIN_FLOOR = 1.0e-5
 EPS64 = float(np.finfo(np.float64).eps)
 EPS32 = float(np.finfo(np.float32).eps)
@@ -28,16 +26,6 @@ EPS32 = float(np.finfo(np.float32).eps)
 # leaves an odd partial last block to both
 FRAMES = (1, 64, 65, 256, 257, 515)
 BIG_FRAMES = (65, 257)               # 126 / 63 / 64: the Python statement takes ~2 ms per frame there
-
-
-def route_of(shape, env=()):
-    """the kernel launch_plp_tail takes for a shape under the switches in `env`"""
-    bins, order, _ = shape
-    if tuple(shape) == EXACT_SHAPE and 'SNF_PLP_GENERIC_TAIL' not in env and 'SNF_PLP_SMALL_TAIL' not in env:
-        return 'plp_tail_exact_kernel'
-    if bins <= SMALL_BINS and order <= SMALL_LPC and 'SNF_PLP_GENERIC_TAIL' not in env:
-        return 'plp_tail_small_kernel'
-    return 'plp_tail_kernel'
 
 
 # (id, shape, processor options, environment): every route, its bound shapes, the switches and the powf branch

@@ -1,8 +1,10 @@
 """Batch layouts for the route tests of the delta, pitch-post and CMVN kernels (test_post_routes.py and
 test_post_routes_gpu.py): lists of utterance lengths whose concatenation, cut into tiles of R rows, puts an
 utterance boundary on every kind of tile seam.  The tile heights are restated here, not read from the source:
-a change of kernels_post.hip that moves a seam has to be made here too, and `check_seams` then says what the
-layouts no longer reach.
+a change of shennong_amd/csrc/post_route.h that moves a seam has to be made here too, and `check_seams` then says
+what the layouts no longer reach.  The four launch ladders of that header are restated here as well (`plp_route_of`,
+`delta_route_of`, `pitch_route_of`, `cmvn_row_groups`): the GPU tests take their expected kernel names from them, and
+test_post_route.py compares them with the header itself on the CPU.
 
 The second half holds the layouts and restated launch arithmetic of the remaining kernels of the path
 (test_post_remaining.py, test_post_remaining_gpu.py): the 256-thread stride loop of vad_threshold_kernel, the 64
@@ -25,6 +27,68 @@ def flat_rows(cols):
 
 
 assert [flat_rows(d) for d in FLAT_COLS] == [132, 72, 40, 36]
+
+
+# ---- the launch ladders, restated ----------------------------------------------------------------------------------
+LDS_LIMIT = 48 * 1024    # dynamic LDS a workgroup of this path asks for at the most
+PLP_EXACT_ROWS = 256     # frames per workgroup of plp_tail_exact_kernel
+PLP_SMALL_ROWS = 64      # ... of plp_tail_small_kernel and plp_tail_kernel
+PLP_MAX_BINS, PLP_MAX_LPC = 126, 63          # kMaxBins, kMaxLpc
+PLP_SMALL_BINS, PLP_SMALL_LPC = 32, 16       # the bound of plp_tail_small_kernel<32, 16>
+PLP_EXACT_SHAPE = (23, 12, 13)               # (mel bins, LPC order, cepstra) of plp_tail_exact_kernel<23, 12, 13>
+PLP_REFUSAL = 'PLP: num_bins > 126 or lpc_order > 63 not supported'
+
+
+def plp_route_of(shape, env=()):
+    """the kernel launch_plp_tail takes for a shape under the switches in `env`"""
+    bins, order, _ = shape
+    if tuple(shape) == PLP_EXACT_SHAPE and 'SNF_PLP_GENERIC_TAIL' not in env and 'SNF_PLP_SMALL_TAIL' not in env:
+        return 'plp_tail_exact_kernel'
+    if bins <= PLP_SMALL_BINS and order <= PLP_SMALL_LPC and 'SNF_PLP_GENERIC_TAIL' not in env:
+        return 'plp_tail_small_kernel'
+    return 'plp_tail_kernel'
+
+
+def delta_n_scales(order, window):
+    """entries of DeltaParams::scales: 2 i window + 1 taps for every order i"""
+    return sum(2 * i * window + 1 for i in range(order + 1))
+
+
+def delta_tiled_lds(order, window, cols, table=True):
+    """LDS bytes of delta_tiled_kernel; without the scale table, of delta_tiled_fixed_kernel"""
+    lds = 2 * 4 * 256 + 4 * (256 + 2 * order * window) * cols
+    return lds + 4 * ((delta_n_scales(order, window) + 3) & ~3) if table else lds
+
+
+def delta_route_of(order, window, cols, records=True, aligned=True):
+    """launch_deltas' choice; `records`: the caller gave a buffer for the tile records, `aligned`: input and output
+    are 16-byte aligned"""
+    if order == 2 and window == 2 and cols in FLAT_COLS and records and aligned:
+        return 'delta_flat_o2w2_kernel'
+    if delta_tiled_lds(order, window, cols) <= LDS_LIMIT and cols <= 256:
+        return 'delta_tiled_fixed_kernel' if window == 2 and order in (1, 2) else 'delta_tiled_kernel'
+    return 'delta_kernel'
+
+
+def pitch_halos(left, right, window):
+    """frames that pitch_post_tiled_kernel stages before and behind its 256 rows"""
+    return max(left, window, 0), max(right, window, 0)
+
+
+def pitch_lds(left, right, window):
+    """LDS bytes of pitch_post_tiled_kernel: a POV weight and a log pitch per staged frame"""
+    return 2 * 4 * (PITCH_POST_ROWS + sum(pitch_halos(left, right, window)))
+
+
+def pitch_route_of(left, right, window, per_frame=False):
+    if pitch_lds(left, right, window) <= LDS_LIMIT and not per_frame:
+        return 'pitch_post_tiled_kernel'
+    return 'pitch_post_kernel'
+
+
+def cmvn_row_groups(cols):
+    """R: the rows of an utterance that cmvn_stats_kernel's 256 threads reduce in parallel"""
+    return max(1, 256 // cols)
 
 
 def offsets_of(lengths):
@@ -149,7 +213,7 @@ CMVN_WEIGHTS = ('none', 'some_zero', 'one_utterance_all_zero')
 
 def cmvn_lengths(cols):
     """utterance lengths around the R = 256 // cols rows that cmvn_stats_kernel reduces in parallel"""
-    r = max(1, 256 // cols)
+    r = cmvn_row_groups(cols)
     return [0, 1, r - 1, r, r + 1, 1000]
 
 

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import post_layouts
 from conftest import assert_close
 from oracle import oracle as orc
 from shennong_amd import Audio, _abi, _backend, synth
@@ -104,10 +105,8 @@ def _plp_tail_kernel(proc):
 
 
 def _plp_tail_route(proc):
-    """launch_plp_tail's routing (kernels_post.hip), restated"""
-    if (proc.num_bins, proc.lpc_order, proc.num_ceps) == (23, 12, 13):
-        return 'plp_tail_exact_kernel'
-    return 'plp_tail_small_kernel' if proc.num_bins <= 32 and proc.lpc_order <= 16 else 'plp_tail_kernel'
+    """launch_plp_tail's routing as post_layouts.py restates it"""
+    return post_layouts.plp_route_of((proc.num_bins, proc.lpc_order, proc.num_ceps))
 
 
 @pytest.mark.parametrize('opts', [dict(), dict(num_ceps=12), dict(num_bins=40)],

@@ -1,4 +1,4 @@
-"""The three routes of launch_plp_tail and rasta_kernel (kernels_post.hip) alone, on chosen mel rows through
+"""The three routes of launch_plp_tail and rasta_kernel (kernels_plp_tail.hip) alone, on chosen mel rows through
 Plan.debug_plp_tail (snf_debug_plp_tail runs launch_rasta and launch_plp_tail as the product path does, without the
 mel front end), against the float64 statement of the tail (oracle/spec_f64.py plp_tail) on the same float32 rows.
 test_plp_tail.py shows on the CPU that the cases of plp_tail_cases.py reach what they claim.

@@ -1,6 +1,6 @@
 """The five kernels of the post-processing path that the route tests left out - vad_threshold_kernel / vad_kernel,
-sliding_cmvn_kernel, concat_columns_kernel, count_nonfinite_kernel (kernels_post.hip) and mfcc_dct_kernel
-(kernels_dct.hip) - on the batches of post_layouts.py, against the statements and derived bounds of post_f64.py.
+sliding_cmvn_kernel (kernels_cmvn.hip), concat_columns_kernel, count_nonfinite_kernel (kernels_post.hip) and
+mfcc_dct_kernel (kernels_dct.hip) - on the batches of post_layouts.py, against the statements and derived bounds of post_f64.py.
 test_post_remaining.py shows on the CPU that the layouts reach their seams, that no VAD frame lies in the band a
 float64 statement cannot decide, and that the float32 C oracle meets the same bounds on the same inputs.  Every test
 asserts its route through Plan.kernel_name where a plan exists and prints its worst error over bound (run with -s;

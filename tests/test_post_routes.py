@@ -13,7 +13,8 @@ from shennong_amd.processor import KaldiPitchPostProcessor
 
 
 def test_tile_heights():
-    """the heights restated in post_layouts.py are those of kernels_post.hip"""
+    """the heights restated in post_layouts.py are those of shennong_amd/csrc/post_route.h (kFlatTileBytes and
+    flat_rows, kDeltaRows, kPostRows; test_post_route.py reads them from the header itself)"""
     assert [lay.flat_rows(d) for d in (13, 23, 40, 43)] == [132, 72, 40, 36]
     assert lay.DELTA_TILED_ROWS == 256 and lay.PITCH_POST_ROWS == 256
 
@@ -62,16 +63,8 @@ def test_delta_cases_cover_every_route():
     assert routes == {'delta_flat_o2w2_kernel', 'delta_tiled_fixed_kernel', 'delta_tiled_kernel', 'delta_kernel'}
     assert {c[3] for c in lay.DELTA_CASES if c[0] == 'delta_flat_o2w2_kernel'} == set(lay.FLAT_COLS)
     for route, order, window, cols, name in lay.DELTA_CASES:
-        # launch_deltas' choice, restated: LDS bytes of the tiled kernels
-        n_scales = sum(2 * i * window + 1 for i in range(order + 1))
-        lds = 2 * 4 * 256 + 4 * ((n_scales + 3) & ~3) + 4 * (256 + 2 * order * window) * cols
-        if order == 2 and window == 2 and cols in lay.FLAT_COLS:
-            want = 'delta_flat_o2w2_kernel'
-        elif lds <= 48 * 1024 and cols <= 256:
-            want = 'delta_tiled_fixed_kernel' if window == 2 and order in (1, 2) else 'delta_tiled_kernel'
-        else:
-            want = 'delta_kernel'
-        assert route == want, (route, order, window, cols)
+        # launch_deltas' choice as post_layouts.py restates it (a record buffer, aligned pointers)
+        assert route == lay.delta_route_of(order, window, cols), (route, order, window, cols)
 
 
 def test_delta_k():

@@ -1,4 +1,5 @@
-"""Every launch route of launch_deltas, launch_pitch_post and launch_cmvn_stats (kernels_post.hip), on batches whose
+"""Every launch route of launch_deltas, launch_pitch_post and launch_cmvn_stats (kernels_delta.hip,
+kernels_pitch_post.hip, kernels_cmvn.hip; the ladders: post_route.h, on the CPU in test_post_route.py), on batches whose
 utterance boundaries sit on every kind of tile seam (post_layouts.py), against the float64 statements with the
 derived bounds of post_f64.py.  test_post_routes.py shows on the CPU that the float32 C oracle meets the same bounds
 on the same inputs.  Every test asserts the route through Plan.kernel_name and prints its worst error over bound
@@ -122,7 +123,7 @@ def test_delta_pointers_off_the_16_byte_grid(gpu, cross_route_input, which):
         _check_delta(f'{which} pointer + {skew} bytes, {route}', _split(out, lengths), mats, 2, 2)
         outs.append(out)
     assert np.array_equal(outs[0], outs[2])
-    # "the same products in the same order" (kernels_post.hip): the two routes agree bit for bit
+    # "the same products in the same order" (kernels_delta.hip): the two routes agree bit for bit
     assert np.array_equal(outs[0], outs[1])
 
 
