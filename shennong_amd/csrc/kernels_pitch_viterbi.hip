@@ -564,11 +564,12 @@ int launch_pitch(const PitchDevTables& t, const PitchBatch& b, const PitchScratc
   if (b.max_down > 0x7fffff00)
     return set_error(SNF_E_RUNTIME, "pitch: an utterance of more than 2^31 resampled samples");
   const PitchKnobs knobs = pitch_knobs_from_env();
+  // (a state space no form runs is refused before the front end: no kernel of the call is launched)
+  const PitchRoute route = pitch_viterbi_route(t.num_states, b.n_utts, knobs);
+  if (route.refusal) return set_error(SNF_E_RUNTIME, route.refusal);
   bool stop = false;
   const int rc = launch_pitch_front(t, b, w, knobs.trace, stream, &stop);
   if (rc != SNF_OK || stop) return rc;
-  const PitchRoute route = pitch_viterbi_route(t.num_states, b.n_utts, knobs);
-  if (route.refusal) return set_error(SNF_E_RUNTIME, route.refusal);
   if (route.form == kPitchFlat) {
     const int flat_rc = launch_pitch_viterbi_flat(t, b, w, route.lds_bytes, out, stream);
     if (flat_rc != SNF_OK) return flat_rc;
