@@ -1008,6 +1008,11 @@ int snf_debug_plp_tail(snf_plan* plan, const float* mel, const double* energy,
    every frame set (32 bits per lane), 0 when it keeps 64-bit addresses: three consecutive utterances that
    span 2^30 samples or more, or SNF_FBANK512B_ADDR64=1 in the environment.  Negative: an error code. */
 int snf_debug_fbank512b_rel32(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts);
+/* Test aid: the frame sets [*lo, *hi) that workgroup `block` of `blocks` of fbank512b_kernel deals to its waves
+   when the batch holds `n_sets` sets of four frames.  The shares tile [0, n_sets) in order and differ by at
+   most one set.  Returns the number of workgroups the launcher starts for `n_sets` (min(256, ceil(n_sets /
+   16))), or a negative error code. */
+int snf_debug_fbank512b_share(int64_t n_sets, int64_t blocks, int64_t block, int64_t* lo, int64_t* hi);
 /* Duration in milliseconds of the kernels launched by the last run call on this plan, measured
    with HIP events on the stream the kernels were launched on.  `which` selects a kernel slot:
    0 = whole call, 1.. = per-kernel; returns <0 if the slot was not recorded. */

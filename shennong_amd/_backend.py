@@ -34,7 +34,7 @@ EXPORTS = [
     'snf_cmvn_apply_device', 'snf_concat_columns_device', 'snf_count_nonfinite_device', 'snf_set_noise_call',
     'snf_malloc', 'snf_free', 'snf_memcpy_h2d', 'snf_memcpy_d2h', 'snf_memset',
     'snf_host_malloc', 'snf_host_free', 'snf_debug_fill_lds', 'snf_debug_pitch_scratch',
-    'snf_debug_plp_tail', 'snf_debug_fbank512b_rel32',
+    'snf_debug_plp_tail', 'snf_debug_fbank512b_rel32', 'snf_debug_fbank512b_share',
     'snf_stream_create', 'snf_stream_destroy', 'snf_stream_synchronize', 'snf_memcpy_h2d_async',
     'snf_memcpy_d2h_async', 'snf_comm_unique_id', 'snf_comm_init', 'snf_comm_rank', 'snf_comm_world_size',
     'snf_comm_destroy', 'snf_comm_gatherv', 'snf_comm_allreduce_f64',
@@ -138,6 +138,7 @@ def lib():
         L.snf_debug_pitch_scratch.argtypes = [vp] + [C.POINTER(vp)] * 4
         L.snf_debug_plp_tail.argtypes = [vp, pf, C.POINTER(C.c_double), pi64, i64, pf, pf]
         L.snf_debug_fbank512b_rel32.argtypes = [pi64, pi64, i64]
+        L.snf_debug_fbank512b_share.argtypes = [i64, i64, i64, pi64, pi64]
         L.snf_stream_create.argtypes = [C.POINTER(vp)]
         L.snf_stream_destroy.argtypes = [vp]
         L.snf_stream_synchronize.argtypes = [vp]

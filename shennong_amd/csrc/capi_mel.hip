@@ -562,4 +562,13 @@ int snf_debug_fbank512b_rel32(const int64_t* sample_offsets, const int64_t* fram
   return fbank512b_rel32_ok(sample_offsets, frame_offsets, n_utts) ? 1 : 0;
 }
 
+// Test aid (include/shennong_amd.h): the share of frame sets that workgroup `block` of fbank512b_kernel deals to its
+// waves, a host function of the three numbers (no plan, no device).
+int snf_debug_fbank512b_share(int64_t n_sets, int64_t blocks, int64_t block, int64_t* lo, int64_t* hi) {
+  if (!lo || !hi) return set_error(SNF_E_INVALID, "null output");
+  if (n_sets < 0 || blocks < 0 || block < 0 || block > blocks) return set_error(SNF_E_INVALID, "no such workgroup");
+  fbank512b_share(n_sets, blocks, block, lo, hi);
+  return static_cast<int>(fbank512b_blocks(n_sets));  // (the workgroups the launcher starts for n_sets: at most 256)
+}
+
 }  // extern "C"

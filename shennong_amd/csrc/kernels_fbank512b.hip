@@ -97,14 +97,44 @@ constexpr int kTileBytes = kFast512TileBytes;     // wave-private LDS per frame
 // indices are 32-bit.  The host (fbank512b_rel32_ok) sets BatchArgs::rel32_samples only where the starts of any
 // four consecutive frames lie less than 2^30 samples apart and the batch has fewer than 2^30 frames; every other
 // batch, and the NJ = 16 forms, run the addressing of before (REL = false).
-template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV, bool REL>
+// Sets dealt inside the CU (DEAL; profiles/NOTEBOOK.md 4.1g, profiles/fbank512b_balance_*).  The fixed walk
+// (set = blockIdx.x * 16 + wid, += 4096) gives every wave the same number of sets before the first instruction runs,
+// and the launch ends with the slowest of the 4096 waves: the four waves of a SIMD do not progress at the same rate
+// (vector issue goes to the oldest first), and a wave that is done leaves its SIMD short of the three ready waves
+// the vector pipe needs.  With DEAL the workgroup owns the contiguous sets [lo, hi) (fbank512b_share_lo) and its
+// waves take them from a ticket counter in LDS, one dword behind the table blob: the first set of a wave is lo + wid,
+// every later one a single-lane ds_add_rtn_u32 brought to a scalar register.  The software pipeline holds three set
+// indices (the set in the registers, the set whose samples are in flight, the set whose frame_start row is in
+// flight); the ticket of the third is drawn in front of the tile writes of phase B, one iteration ahead of its first
+// use, so the round trip stands under the wait of the transpose.  A ticket at or past hi is no set: the REL forms read
+// 0 rows for it (the row bound is min(total_frames, 4 hi)), the 64-bit forms clamp as before, and the wave leaves when
+// the set in its registers is one.  Which wave transforms a set does not enter the set's arithmetic.  Consecutive
+// tickets are consecutive sets (60 % of their samples shared), like the sets of wid and wid + 1 before.  Forms that
+// would spill with the two scalar indices and the ticket register keep the fixed walk (launch_deal).
+// SNF_FBANK512B_STAMPS (off in the library; tools/fbank512b_stamps.cpp builds it): every wave writes its workgroup,
+// wave, XCC and hardware ids, both clocks at entry to and exit from the set loop and its number of sets to a debug
+// buffer, with ordinary vector stores of lane 0 behind the loop.
+#ifdef SNF_FBANK512B_STAMPS
+#define SNF_STAMP_PARAM , unsigned long long* __restrict__ stamps
+#define SNF_STAMP_ARG , g_stamps
+constexpr int kStampWords = 8;  // per wave: ids, XCC id, HW id, sets, s_memtime in / out, s_memrealtime in / out
+unsigned long long* g_stamps = nullptr;
+#else
+#define SNF_STAMP_PARAM
+#define SNF_STAMP_ARG
+#endif
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV, bool REL, bool DEAL>
 __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512Params p, const BatchArgs b,
                                                                   float* __restrict__ out,
-                                                                  double* __restrict__ energy_out) {
+                                                                  double* __restrict__ energy_out,
+                                                                  const Fast512bShares shares SNF_STAMP_PARAM) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* tab = reinterpret_cast<float*>(smem);
   // ---- stage the tables into LDS (the only workgroup-wide barrier of the kernel) -------------------
   for (int i = threadIdx.x; i < p.table_floats; i += kWaves * 64) tab[i] = p.tables[i];
+  // DEAL: the ticket counter, relative to the first set of the workgroup (tickets 0 .. 15 are the waves' first sets)
+  unsigned* const ticket = reinterpret_cast<unsigned*>(tab + p.table_floats);
+  if (DEAL && threadIdx.x == 0) *ticket = kWaves;
   __syncthreads();
   const float2* __restrict__ t_win = reinterpret_cast<const float2*>(tab + kHeaderFloats);
   const float2* __restrict__ t_tw16 = t_win + 16 * 18;
@@ -116,7 +146,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
   // (wid through readfirstlane: the set index and everything derived from it stay in scalar registers)
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int l = lane & 15, q = lane >> 4;
-  const int tab_bytes = (p.table_floats * 4 + 255) & ~255;
+  const int tab_bytes = ((p.table_floats + (DEAL ? 1 : 0)) * 4 + 255) & ~255;  // (launch_form: the same sum)
   char* wave_base = smem + tab_bytes + (wid * 4 + q) * kTileBytes;
   float2* tile = reinterpret_cast<float2*>(wave_base);  // 16 rows x 17 complex
   // power tile [257]: aliases the frame tile.  The frame tiles are 544 floats apart (bank offset 0, 32, 0,
@@ -157,8 +187,33 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
   const idx_t n_sets = (total_frames + 3) >> 2;
   const idx_t set_stride = static_cast<idx_t>(gridDim.x) * kWaves;
   const idx_t last_frame = total_frames - 1;
-  idx_t set = static_cast<idx_t>(blockIdx.x) * kWaves + wid;
-  if (set >= n_sets) return;
+  // DEAL: the sets [set_lo, set_end) of this workgroup; the fixed walk: every 4096th set of the batch
+  const idx_t set_lo = DEAL ? static_cast<idx_t>(fbank512b_share_lo(shares, blockIdx.x)) : 0;
+  const idx_t set_end = DEAL ? static_cast<idx_t>(fbank512b_share_lo(shares, blockIdx.x + 1)) : n_sets;
+  idx_t set = DEAL ? set_lo + wid : static_cast<idx_t>(blockIdx.x) * kWaves + wid;
+  if (set >= set_end) return;
+  // (DEAL: the frames in front of the end of the share - a set at or past it has no rows)
+  const idx_t frames_end = DEAL && set_end * 4 < total_frames ? set_end * 4 : total_frames;
+  // A ticket: lane 0 alone draws (ds_add_rtn_u32 under an exec of one lane); set_of waits for the value and brings
+  // it to a scalar register.  Two asm statements, each with its own instruction(s) and nothing else: as an atomic
+  // builtin under `if (lane == 0)` the compiler's atomic optimizer adds a count of the active lanes and a full wait
+  // directly behind the draw, and the branch cuts the phase in two.  The value is not to be touched between the two
+  // statements (the compiler does not know it is in flight): it has one use, in set_of.
+  const unsigned ticket_addr = lds_addr(ticket), ticket_one = 1u;
+  auto draw = [&]() -> unsigned {
+    unsigned t;
+    unsigned long long keep;
+    asm volatile("s_mov_b64 %1, exec\n\ts_mov_b64 exec, 1\n\tds_add_rtn_u32 %0, %2, %3\n\ts_mov_b64 exec, %1"
+                 : "=&v"(t), "=&s"(keep)
+                 : "v"(ticket_addr), "v"(ticket_one)
+                 : "memory");
+    return t;
+  };
+  auto set_of = [&](unsigned t) -> idx_t {
+    unsigned s;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\tv_readfirstlane_b32 %0, %1" : "=s"(s) : "v"(t) : "memory");
+    return set_lo + static_cast<idx_t>(s);
+  };
 
   // NJ = 13: the 25 ms / 16 kHz window (only element j = 12 can fall outside it); NJ = 16: any other
   // window that pads to 512 samples, with a per-element test
@@ -173,7 +228,7 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
   // the last frame again: its features are computed from whatever the sample buffer gives and never stored.
   const unsigned q8 = static_cast<unsigned>(q) * 8u;
   auto set_rows_of = [&](const void* table, idx_t s) -> uint64_t {
-    int rows = static_cast<int>(total_frames) - static_cast<int>(s) * 4;
+    int rows = static_cast<int>(frames_end) - static_cast<int>(s) * 4;
     rows = rows < 0 ? 0 : rows;
     asm volatile("" : "+s"(rows));  // (two scalar instructions: as one clamp the compiler takes v_med3_i32)
     rows = rows > 4 ? 4 : rows;
@@ -233,8 +288,18 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
   // 4 waves per SIMD leave it, and LDS bandwidth is what it is short of (4 ds_read_b128 per set less)
   float4 w512q[4];
   read_quads<4>(t_tw512 + l * 10, w512q);
-  int64_t start_next = start_of(set + set_stride);
-  unsigned long long noise_cur = noise_of(set), noise_next = noise_of(set + set_stride);
+  // the set whose samples are requested next and the one whose table rows are (DEAL: two tickets; the fixed walk
+  // forms them from `set` where it uses them)
+  idx_t set_n1 = 0, set_n2 = 0;
+  if (DEAL) {
+    const unsigned t1 = draw(), t2 = draw();
+    set_n1 = set_of(t1);
+    set_n2 = set_of(t2);
+  }
+  auto ahead1 = [&]() -> idx_t { return DEAL ? set_n1 : set + set_stride; };
+  auto ahead2 = [&]() -> idx_t { return DEAL ? set_n2 : set + 2 * set_stride; };
+  int64_t start_next = start_of(ahead1());
+  unsigned long long noise_cur = noise_of(set), noise_next = noise_of(ahead1());
   request(start_of(set));
   if (BST) {
     // one dropped store behind the first request: the loop is entered with the same sequence of vector-
@@ -244,8 +309,14 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     if (KIND == SNF_KIND_MFCC) __builtin_amdgcn_raw_buffer_store_b32(0u, none, -1, 0, 0);
     else __builtin_amdgcn_raw_buffer_store_b128(u32x4{0u, 0u, 0u, 0u}, none, -1, 0, 2);
   }
+#ifdef SNF_FBANK512B_STAMPS
+  unsigned long long stamp_in, stamp_in_real;
+  unsigned stamp_sets = 0;
+  asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_in), "=s"(stamp_in_real)
+               : : "memory");
+#endif
 
-  for (; set < n_sets; set += set_stride) {
+  while (set < set_end) {
     const idx_t g = set * 4 + q;  // global frame = output row
     const bool valid = g <= last_frame;
 
@@ -285,10 +356,10 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
     for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(xe[j]), "+v"(xo[j]) : : "memory");
     asm volatile("" : "+v"(part) : : "memory");
     request(start_next);  // (the final request of a wave re-reads the last frame)
-    start_next = start_of(set + 2 * set_stride);
+    start_next = start_of(ahead2());
     if (DITHER) {
       noise_cur = noise_next;
-      noise_next = noise_of(set + 2 * set_stride);
+      noise_next = noise_of(ahead2());
     }
 
     float neg_mean = 0.0f;
@@ -345,6 +416,10 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
 
     // ---- B: pass 1 (FFT over j), inter-pass twiddle W256^(l k2), 16 x 16 transpose -----------------
     fft16_lf(z);
+    // DEAL: the ticket of the set whose table rows the NEXT iteration requests, in front of the tile writes - the
+    // LDS serves a wave in order, so it has landed when the transposed row below has
+    unsigned ticket_n3 = 0;
+    if (DEAL) ticket_n3 = draw();
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) tile[k2 * kTileRow + l] = z[k2];
     wave_lds_order();
@@ -360,6 +435,8 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
         ct[m + 1] = make_float2(tw4[m >> 1].z, tw4[m >> 1].w);
       }
     }
+    idx_t set_n3 = 0;
+    if (DEAL) set_n3 = set_of(ticket_n3);
     __builtin_amdgcn_sched_barrier(0);
     // ---- C: pass 2 (twiddle + FFT over n1): z[k1] = Z[l + 16 k1] -----------------------------------
     fft16_twin(z, ct);
@@ -648,7 +725,35 @@ __global__ __launch_bounds__(kWaves * 64, 4) void fbank512b_kernel(const Fast512
       }
     }
     wave_lds_order();  // the tile is reused by the next frame set
+    if (DEAL) {
+      set = set_n1;
+      set_n1 = set_n2;
+      set_n2 = set_n3;
+    } else {
+      set += set_stride;
+    }
+#ifdef SNF_FBANK512B_STAMPS
+    ++stamp_sets;
+#endif
   }
+#ifdef SNF_FBANK512B_STAMPS
+  {
+    unsigned long long stamp_out, stamp_out_real;
+    asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_out), "=s"(stamp_out_real)
+                 : : "memory");
+    if (stamps != nullptr && lane == 0) {
+      unsigned long long* mine = stamps + (static_cast<size_t>(blockIdx.x) * kWaves + wid) * kStampWords;
+      mine[0] = (static_cast<unsigned long long>(blockIdx.x) << 8) | static_cast<unsigned>(wid) | (1ull << 63);
+      mine[1] = __builtin_amdgcn_s_getreg(20 | (31 << 11));  // HW_REG_XCC_ID, all 32 bits
+      mine[2] = __builtin_amdgcn_s_getreg(4 | (31 << 11));   // HW_REG_HW_ID: wave slot, SIMD, CU, SH, SE
+      mine[3] = stamp_sets;
+      mine[4] = stamp_in;
+      mine[5] = stamp_out;
+      mine[6] = stamp_in_real;
+      mine[7] = stamp_out_real;
+    }
+  }
+#endif
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -704,22 +809,54 @@ bool fbank512b_eligible(const Fast512Params& p, const BatchArgs& b) {
   return fbank512b_shape_ok(p, b.blk_utt != nullptr);
 }
 
+// The shares of the workgroups (DEAL): see Fast512bShares.  One workgroup per CU, fewer for a batch of fewer than 16
+// sets each: at least one set per wave of every workgroup but the last.
+int64_t fbank512b_blocks(int64_t n_sets) {
+  const int64_t blocks = (n_sets + kWaves - 1) / kWaves;
+  return blocks > 256 ? 256 : blocks;
+}
+void fbank512b_share(int64_t n_sets, int64_t blocks, int64_t b, int64_t* lo, int64_t* hi) {
+  const Fast512bShares s = fbank512b_shares(n_sets, blocks);
+  *lo = fbank512b_share_lo(s, b);
+  *hi = fbank512b_share_lo(s, b + 1);
+}
+// SNF_FBANK512B_FIXED=1 keeps every batch on the fixed walk (A/B runs; read at every call, like SNF_FBANK512_OLD)
+static bool fbank512b_fixed_knob() {
+  const char* knob = getenv("SNF_FBANK512B_FIXED");
+  return knob && knob[0] == '1';
+}
+
 namespace {
 
-template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV, bool REL>
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV, bool REL, bool DEAL>
 int launch_form(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
-  const size_t lds = fast512_lds_bytes(q.table_floats, kWaves, false);
+  // (DEAL: the ticket counter is one dword behind the table blob, in front of the tiles)
+  const size_t lds = fast512_lds_bytes(q.table_floats + (DEAL ? 1 : 0), kWaves, false);
   const int64_t n_sets = (b.total_frames + 3) / 4;
-  int64_t blocks = (n_sets + kWaves - 1) / kWaves;
-  if (blocks > 256) blocks = 256;  // one resident workgroup per CU, grid-stride over the frame sets
-  auto kern = fbank512b_kernel<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, REL>;
+  const int64_t blocks = fbank512b_blocks(n_sets);  // one resident workgroup per CU
+  auto kern = fbank512b_kernel<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, REL, DEAL>;
   if (lds > 64 * 1024)
     SNF_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)));
   hipLaunchKernelGGL(kern, dim3(static_cast<unsigned>(blocks)), dim3(kWaves * 64), lds, stream, q, b, out,
-                     energy_out);
+                     energy_out, fbank512b_shares(n_sets, blocks) SNF_STAMP_ARG);
   SNF_HIP_CHECK(hipGetLastError());
   return SNF_OK;
+}
+
+// Sets dealt to the waves of a workgroup as they finish (DEAL) or the fixed walk over every 4096th set.  The fixed
+// walk stays for the forms that have no register left for the ticket (kDealFits: scratch in the listing with it,
+// none without), for a table blob that fills the LDS to the last dword, and behind SNF_FBANK512B_FIXED=1.
+template <int NJ, int KIND, int ENERGY, bool BST, bool DITHER, int MMQ, int LV, bool REL>
+int launch_deal(const Fast512Params& q, const BatchArgs& b, float* out, double* energy_out, hipStream_t stream) {
+  // (the listing: the NJ = 16 forms gain up to 80 bytes of scratch with DEAL, MFCC with dither on the 7-quad plans
+  // 8 bytes, and so do some MFCC forms without the single store, which no plan launches; all others none)
+  constexpr bool kDealFits = NJ == 13 && !(KIND == SNF_KIND_MFCC && (!BST || (DITHER && MMQ == 7)));
+  if constexpr (kDealFits) {
+    if (!fbank512b_fixed_knob() && fast512_lds_bytes(q.table_floats + 1, kWaves, false) <= kFast512LdsBytes)
+      return launch_form<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, REL, true>(q, b, out, energy_out, stream);
+  }
+  return launch_form<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, REL, false>(q, b, out, energy_out, stream);
 }
 
 // Set-relative sample addressing (REL) where the host found the batch's frame starts close enough
@@ -729,9 +866,9 @@ int launch_dither(const Fast512Params& q, const BatchArgs& b, float* out, double
   // (MFCC with dither on the 7-quad, 3-block plan: spills 2-4 registers with it, none without)
   if constexpr (NJ == 13 && !(KIND == SNF_KIND_MFCC && DITHER && MMQ == 7 && LV == 3)) {
     if (b.rel32_samples > 0)
-      return launch_form<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, true>(q, b, out, energy_out, stream);
+      return launch_deal<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, true>(q, b, out, energy_out, stream);
   }
-  return launch_form<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, false>(q, b, out, energy_out, stream);
+  return launch_deal<NJ, KIND, ENERGY, BST, DITHER, MMQ, LV, false>(q, b, out, energy_out, stream);
 }
 
 // The mel plan as a compile-time property of the launch (NJ = 13): chain length 7 / 6 quads and 2-3 / 4 blocks per
@@ -845,3 +982,11 @@ int launch_fbank512b(const Fast512Params& p, const BatchArgs& b, float* out, int
 }
 
 }  // namespace snf
+
+#ifdef SNF_FBANK512B_STAMPS
+// the stamp build alone: where the launches that follow write their waves' records (device memory, 8 x 64-bit words
+// per wave, 4096 waves; nullptr: nowhere)
+extern "C" __attribute__((visibility("default"))) void snf_debug_fbank512b_stamps(void* device_buffer) {
+  snf::g_stamps = static_cast<unsigned long long*>(device_buffer);
+}
+#endif

@@ -314,6 +314,27 @@ bool fbank512b_addr64_knob();
 bool fbank512b_rel32_ok(const int64_t* sample_offsets, const int64_t* frame_offsets, int64_t n_utts);
 int launch_fbank512b(const Fast512Params& p, const BatchArgs& b, float* out, int out_cols,
                      double* energy_out, hipStream_t stream);
+// fbank512b_kernel deals the frame sets to the waves of a workgroup as they finish (DEAL): workgroup b of
+// `blocks` owns the contiguous sets [lo, hi), the shares tile [0, n_sets) in order and differ by at most one
+// set: n_sets = blocks * base + rem, and the first `rem` shares hold base + 1.  The quotient is formed once, in
+// 64 bits, on the host; the kernel gets (base, rem) and forms its lo and hi in scalar registers.
+struct Fast512bShares {
+  int64_t base;
+  int64_t rem;
+};
+inline Fast512bShares fbank512b_shares(int64_t n_sets, int64_t blocks) {
+  return blocks > 0 ? Fast512bShares{n_sets / blocks, n_sets % blocks} : Fast512bShares{0, 0};
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int64_t fbank512b_share_lo(const Fast512bShares& s, int64_t b) {
+  return b * s.base + (b < s.rem ? b : s.rem);
+}
+// ... as a host function of its own (tests/test_fbank512b_share.py through snf_debug_fbank512b_share)
+void fbank512b_share(int64_t n_sets, int64_t blocks, int64_t b, int64_t* lo, int64_t* hi);
+// workgroups of a launch over n_sets frame sets: one per CU, fewer for a batch of fewer than 16 sets each
+int64_t fbank512b_blocks(int64_t n_sets);
 
 // ---- register-resident 2048-point path (kernels_fbank2048.hip): frames that pad to 2048 samples (44.1 / 48 kHz)
 bool fbank2048_eligible(const MelParams& mp);
